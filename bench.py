@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — gate-application throughput on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1 without a torch.distributed environment re-launches itself as N ranks (one per GPU) under
 torch.distributed.run on 127.0.0.1; under an existing launcher (RANK / WORLD_SIZE set) it runs as that rank.
@@ -17,7 +17,8 @@ steps, warmup, ms_per_step, dtype, config, roofline, cpu_baseline, parity_ok, a 
 per_gpu_efficiency / comm.  It is printed as soon as the headline, its parity check and the CPU baseline are done
 (flushed), and printed again as the final line once the extras have run, so a problem in an extras leg cannot cost the
 headline.  Everything else — every parity leg, per-kernel figures, the extras — goes to bench_detail.json beside this
-file (rewritten after every leg).
+file (rewritten after every leg).  --dump-outputs DIR also writes the state the last timed step left, as DIR/*.npy
+(dump_outputs), so that two builds can be compared output for output.
 
 Order of work (N = 1):
   1. parity, core   the timed configuration against the CPU ORACLE before anything is timed: seeded product state with
@@ -50,7 +51,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
+HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak
 REPS = 5                # repetitions of every extras leg (median reported)
 T_START = time.perf_counter()
 DETAIL_PATH = os.environ.get("QIP_BENCH_DETAIL", os.path.join(ROOT, "bench_detail.json"))
@@ -79,7 +80,12 @@ def parse_args(argv=None):
     ap.add_argument("--only", default="", help="comma-separated extras sections to run (default: all that fit)")
     ap.add_argument("--dist-overlap", type=int, default=0,
                     help="N > 1 only, experimental: add legs with the exchange cut into this many slices (option dist_overlap)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the state they left (a fixed seeded sample of its amplitudes) as DIR/*.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def self_spawn(args) -> int:
@@ -314,6 +320,32 @@ def make_roofline(kname, kstat, n_local):
             "traffic_source": f"static: {traffic_src} (separate rocprofv3 --pmc passes of this command)" if traffic_src else None,
             "traffic_stale": traffic_stale, "avg_launch_ms": avg_ms, "launches": kstat["launches"],
             "algorithmic_bytes_per_launch": per_launch_bytes}
+
+
+DUMP_SAMPLE = 1 << 20  # amplitudes written by --dump-outputs: 2^20 x (re, im) plus their indices, 24 MiB of float64
+
+
+def dump_outputs(out_dir, st, n, norm, rank):
+    """--dump-outputs: what the timed path hands its caller after the last timed step, the resident state vector, as .npy files:
+    state.npy (m x 2 float64: re, im), state_index.npy (the logical index of each row, float64: exact below 2^53) and norm_sqr.npy
+    (over all 2^n amplitudes).  The whole vector up to DUMP_SAMPLE amplitudes, above that a fixed seeded sample of DUMP_SAMPLE
+    indices (sorted, duplicates dropped): the same rows on every run with the same arguments.  Read with the index gather,
+    never through the timed path; collective for a sharded state (rank 0 writes).  Returns the files' total bytes."""
+    import numpy as np
+
+    if (1 << n) <= DUMP_SAMPLE:
+        idx = np.arange(1 << n, dtype=np.uint64)
+    else:
+        idx = np.unique(np.random.default_rng(28).integers(0, 1 << n, size=DUMP_SAMPLE, dtype=np.uint64))
+    amps = st.download_logical(idx) if hasattr(st, "download_logical") else st.download_indices(idx)
+    if rank != 0:
+        return 0
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"state": np.stack([amps.real, amps.imag], axis=1).astype(np.float64),
+              "state_index": idx.astype(np.float64), "norm_sqr": np.array([norm], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sum(a.nbytes for a in arrays.values())
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -872,6 +904,9 @@ def main():
         dist.all_reduce(rr, op=dist.ReduceOp.MIN)
         rccl_ranks_min = int(rr.item())
     norm = st.norm_sqr()
+    if args.dump_outputs:  # (before the extras apply anything else to this state)
+        em.detail["_now"] = "dump-outputs"
+        em.detail["dump_outputs"] = {"dir": args.dump_outputs, "bytes": dump_outputs(args.dump_outputs, st, n, norm, rank)}
 
     value = bytes_per_step * args.steps / elapsed / 1e9
     kname, kstat = dominant_kernel(profile)

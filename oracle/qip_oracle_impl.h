@@ -7,7 +7,7 @@
  *   qip-iterators/src/iterators/ops.rs         (per-variant dispatch, nested Control)
  *   qip-iterators/src/iterators/qubit_iterators.rs (the four row iterators)
  *   qip/src/state_ops/measurement_ops.rs       (measurement)
- * Scalar arithmetic follows num-complex ^0.4 (not vendored in /root/reference, version
+ * Scalar arithmetic follows num-complex ^0.4 (not vendored in the reference, version
  * unpinned by a lockfile): Mul = (ac - bd, ad + bc), Add componentwise, Sum = fold(0, +),
  * is_zero = re == 0 && im == 0, norm_sqr = re*re + im*im, Complex * real = (re*p, im*p).
  * Built with -ffp-contract=off so no product is fused into an add (rustc never contracts).

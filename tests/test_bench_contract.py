@@ -71,3 +71,38 @@ def test_bench_cli_contract_without_a_gpu():
                        env=dict(os.environ, QIP_BENCH_DETAIL=os.devnull))
     assert p.returncode != 0 and "needs a HIP device" in (p.stderr + p.stdout)
     assert not [l for l in p.stdout.splitlines() if l.startswith("{")]
+
+
+def test_bench_dump_outputs_flag_and_files(tmp_path):
+    """--dump-outputs DIR parses, --steps 0 is refused, and the writer puts float64 arrays of at most 64 MB under DIR: the whole
+    vector of a small state, a fixed seeded sample (same rows every time) of a large one"""
+    import numpy as np
+    import pytest
+
+    assert bench.parse_args(["--steps", "3", "--dump-outputs", str(tmp_path)]).dump_outputs == str(tmp_path)
+    assert bench.parse_args([]).dump_outputs == ""
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+    class FakeState:  # HipState.download_indices over a host vector whose amplitude k is k + 0.5j
+        def download_indices(self, idx):
+            idx = np.asarray(idx, dtype=np.uint64)
+            assert idx.size and int(idx.max()) < 1 << n
+            return idx.astype(np.float64) + 0.5j
+
+    for n, rows in ((4, 16), (30, None)):
+        dumps = []
+        for rep in range(2):
+            d = tmp_path / f"{n}_{rep}"
+            nbytes = bench.dump_outputs(str(d), FakeState(), n, 0.75, 0)
+            files = {p.name: np.load(p) for p in d.iterdir()}
+            assert set(files) == {"state.npy", "state_index.npy", "norm_sqr.npy"} and nbytes <= 64 << 20
+            assert all(a.dtype == np.float64 for a in files.values()) and sum(a.nbytes for a in files.values()) == nbytes
+            state, index = files["state.npy"], files["state_index.npy"]
+            assert state.shape == (index.size, 2) and np.array_equal(state[:, 0], index) and np.all(state[:, 1] == 0.5)
+            assert files["norm_sqr.npy"].tolist() == [0.75] and np.all(np.diff(index) > 0)
+            assert index.size == rows if rows else bench.DUMP_SAMPLE // 2 < index.size <= bench.DUMP_SAMPLE
+            dumps.append(index)
+        assert np.array_equal(*dumps)
+    assert bench.dump_outputs(str(tmp_path / "rank1"), FakeState(), 4, 1.0, 1) == 0 and not (tmp_path / "rank1").exists()

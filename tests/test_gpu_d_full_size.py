@@ -310,6 +310,43 @@ def test_bench_fails_when_parity_fails(tmp_path):
 
 
 @pytest.mark.slow
+def test_bench_dump_outputs_are_the_timed_state(O, tmp_path):
+    """bench.py --dump-outputs: the sampled amplitudes are those of the state the warm-up + timed steps left (the seeded
+    product state, then the timed circuit W + K times), against the oracle on the same inputs; --steps sets the timed steps."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    from oracle import window_parity as W
+
+    n, gates, steps, warmup = 21, 64, 2, 1  # 2^21 amplitudes: above bench.DUMP_SAMPLE, so the sampled form is what is checked
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--n-local", str(n),
+           "--gates", str(gates), "--headline-only", "--dump-outputs", str(out)]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["QIP_BENCH_DETAIL"] = str(tmp_path / "bench_detail.json")
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root, env=env)
+    assert res.returncode == 0, res.stderr[-2000:]
+    line = json.loads(res.stdout.rstrip().splitlines()[-1])
+    assert line["steps"] == steps and line["ms_per_step"] > 0
+    state, index, norm = (np.load(out / f"{k}.npy") for k in ("state", "state_index", "norm_sqr"))
+    assert state.dtype == index.dtype == norm.dtype == np.float64 and state.shape == (index.size, 2)
+    assert sum(a.nbytes for a in (state, index, norm)) <= 64 << 20
+    idx = index.astype(np.int64)
+    assert np.array_equal(idx, np.unique(idx)) and idx[-1] < (1 << n) and idx.size > (1 << 19)
+    x = np.zeros(1 << n, dtype=np.complex128)
+    x[0] = 1
+    x = O.apply_ops_in_place(n, W.product_state_ops(n, seed=n)[0], x)  # (returns the result: it ping-pongs two buffers)
+    ops = circuits.c2_random_circuit(n, gates, seed=28, single_only=True)
+    for _ in range(warmup + steps):
+        x = O.apply_ops_in_place(n, ops, x)
+    assert np.max(np.abs(state[:, 0] + 1j * state[:, 1] - x[idx])) <= 1e-12
+    assert abs(norm[0] - line["norm_sqr_after"]) <= 1e-12 and abs(norm[0] - 1) <= 1e-9
+
+
+@pytest.mark.slow
 @pytest.mark.parametrize("n", [25])
 def test_full_size_every_timed_leg_with_whole_vector_guard(O, n):
     """What bench.py's parity block does at n = 30, as a test at n = 25 (r5: was 28, r6: 26 — the n = 30 version runs inside every

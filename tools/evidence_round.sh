@@ -4,8 +4,8 @@
 #   bash tools/evidence_round.sh r06 final    the round's LAST GPU call: the full GPU suite, the bench run whose line is committed, smoke
 #   bash tools/evidence_round.sh r06 extras   the headline at n = 33 on ONE GPU (128 GiB), two ranks x 2^29 on one GPU (host-staged
 #                                             transport), the launch-bound regime (n = 8..24), the real-P table
+R=$(cd "$(dirname "$0")/.." && pwd)  # the checkout this script belongs to
 TAG=${1:-r04}
-R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R

@@ -1,9 +1,9 @@
 # rocprofv3 evidence for one round (run on the GPU box through gpurun): kernel stats of the headline bench, the same
 # with every extras leg, and the two separate PMC passes (FETCH_SIZE / WRITE_SIZE cannot share a pass on gfx950).
 # usage: bash tools/profile_round.sh r02        results under gpurun_out/<tag>/prof_*
+R=$(cd "$(dirname "$0")/.." && pwd)  # the checkout this script belongs to
 TAG=${1:-r02}
 cd /tmp && export TMPDIR=/tmp
-R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 sha256sum $R/rustqip_amd/csrc/qip_kernels.h | cut -c1-16 > $O/kernels_sha16.txt   # which kernels these passes describe
