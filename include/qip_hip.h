@@ -324,9 +324,14 @@ int qip_hip_jit_cache_info(uint64_t* resident, uint64_t* evicted, uint64_t* cap)
  *                        time than the compiled sweeps save) uses compiled wide sweeps only when EVERY segment of the plan
  *                        is already resident or in the disk cache, otherwise the interpreter now and the missing segments
  *                        in background helper processes for the next call or process.  0: the state's options as set.
- *   "pair_floor"    [1]  gate-by-gate apply_ops (n >= 22): a gate whose selectors sit inside a 1-KiB wave row (a sweep of the
- *                        whole vector for half / a quarter of the bytes) goes with its neighbour as ONE two-item tile sweep when
- *                        both fit a tile (IEEE-equal).  0: one launch per gate.
+ *   "pair_floor"    [1]  gate-by-gate apply_ops ("tile" = 0, n >= 22): the batch is planned once as tile sweeps in circuit
+ *                        order (exact commutations only, no relabelling, no permutation sweeps) and each step of >= 2 gates
+ *                        runs as ONE interpreter sweep when its gates, launched one by one, would move >= 1.3 sweeps of the
+ *                        vector (a gate's algorithmic share, doubled per selector inside a 1-KiB wave row, at most 1); every
+ *                        other step one launch per gate.  IEEE-equal to one launch per gate; nothing is compiled at run time.
+ *                        Batches of a sharded state with a fold / slice request, program recordings, "fuse" >= 2 and a
+ *                        relabelled state keep the older rule: a gate whose selectors sit inside a wave row goes with its
+ *                        neighbour as one two-item sweep.  0: one launch per gate, always.
  */
 int qip_hip_state_set_option(qip_hip_state* s, const char* key, int64_t value);
 

@@ -2422,6 +2422,71 @@ static int apply_ops_tiled(qip_hip_state* s, const qip_op* ops_in, uint64_t coun
   return QIP_OK;
 }
 
+// Option "pair_floor"'s byte rule: what one gate launched by itself moves, in sweeps of the whole vector — its algorithmic share,
+// doubled for every selector (control, target of a phase-type diagonal) inside a 1-KiB wave row (whole lines / rows travel
+// whichever half is needed: profiles/r02_line_bits.md), at most 1.  false: the op is not a tile item.  `floor_gate`: the doubling
+// applied (the gate moves more than its algorithmic bytes).
+static bool floor_share(const qip_hip_state* s, const qip_op* op, const TileItem& it, double* share, bool* floor_gate) {
+  double by = 0;
+  if (!it.tileable || qip_hip_op_algorithmic_bytes(s->dtype, s->n, op, &by) != QIP_OK) return false;
+  const double full = 2.0 * (double)s->amp_bytes * (double)s->namps;
+  const int in_row = __builtin_popcountll(it.d_mask & 63ull);
+  *share = std::min(1.0, by / full * (double)(1u << in_row));
+  *floor_gate = in_row && *share > by / full;
+  return true;
+}
+// A multi-gate interpreter sweep moves one sweep and runs a little slower than a bare one: it pays from 1.3 sweeps of single
+// launches (T on a low bit + H = 1 + 1; NOT two controlled phases of a QFT, 1/4 doubled = 1/2 each: 946 -> 986 ms when paired).
+constexpr double kFloorFuseSweeps = 1.3;
+
+// Option "pair_floor" on the default path (tile = 0): the WHOLE batch planned once as tile sweeps in circuit order (mode 1:
+// exact commutations only, no relabelling, no permutation sweeps — the state never leaves the caller's order) and every step of
+// >= 2 gates that the byte rule accepts launched as ONE interpreter sweep; every other step gate by gate through the gate's own
+// kernel.  The same unfused arithmetic per amplitude as one launch per gate: IEEE-equal (only the sign of a zero may differ).
+// Interpreter only: nothing is compiled at run time.  A failure leaves a prefix of the (commutation-equivalent) circuit applied
+// in the caller's order, as gate by gate does, and names the caller's op indices (the plan's circuit IS the caller's array).
+template <typename T>
+static int apply_ops_floor_plan(qip_hip_state* s, const TileSchedule& sc) {
+  const int64_t jit = s->tile_jit;
+  s->tile_jit = 0;  // (launch_tile_segment: the interpreter, whatever the tile options of other paths say)
+  int rc = QIP_OK;
+  std::string where;
+  for (const TileStep& st : sc.steps) {
+    bool fuse = st.ops.size() >= 2 && st.perm.empty();
+    double moved = 0;
+    for (size_t j = 0; fuse && j < st.ops.size(); ++j) {
+      double share = 0;
+      bool floor_gate = false;
+      fuse = floor_share(s, &sc.circuit[st.ops[j]], sc.items[st.ops[j]], &share, &floor_gate);
+      moved += share;
+    }
+    if (fuse && moved >= kFloorFuseSweeps) {
+      std::vector<const TileItem*> seg;
+      for (uint64_t i : st.ops) seg.push_back(&sc.items[i]);
+      rc = launch_tile_segment<T>(s, seg, st.high);  // (the profile credits ONE sweep's bytes)
+      if (rc != QIP_OK) {
+        for (uint64_t i : st.ops) where += (where.empty() ? "ops " : ", ") + std::to_string(i);
+        break;
+      }
+      continue;
+    }
+    for (uint64_t i : st.ops) {
+      rc = apply_op_t<T>(s, &sc.circuit[i]);
+      if (rc != QIP_OK) {
+        where = "op " + std::to_string(i);
+        break;
+      }
+    }
+    if (rc != QIP_OK) break;
+  }
+  s->tile_jit = jit;
+  if (rc != QIP_OK) {
+    std::string msg = g_last_error;
+    return fail(rc, "%s: %s", where.c_str(), msg.c_str());
+  }
+  return QIP_OK;
+}
+
 extern "C" int qip_hip_state_apply_ops(qip_hip_state* s, const qip_op* ops, uint64_t count) try {
   STATE_ENTER_RAW(s);  // (a relabelled state stays relabelled for a relabelling batch: apply_ops_tiled decides)
   if (count && !ops) return fail(QIP_ERR_INVALID, "null op array");
@@ -2445,6 +2510,12 @@ extern "C" int qip_hip_state_apply_ops(qip_hip_state* s, const qip_op* ops, uint
     return s->dtype == QIP_C64 ? apply_ops_tiled<double>(s, ops, count, s->tile >= 2)
                                : apply_ops_tiled<float>(s, ops, count, s->tile >= 2);
   }
+  // The batch plan of option pair_floor owns the batch only where nothing else decides its launches: not for a sharded state's
+  // batch that carries a fold / slice request (its last sweep is chosen by the exchange), not while a program records or
+  // pre-compiles, not on a state that arrives relabelled, not under force_generic or fuse
+  const bool floor_plan = s->pair_floor && count >= 2 && s->n >= (uint32_t)kPairFloorMinQubits && s->tile_passes && !s->capture_pool &&
+                          !s->jit_prepare && !s->force_generic && !g_force_generic && s->fuse < 2 && s->layout.empty() &&
+                          !s->fold_request && !s->slice_first && !s->slice_last;
   if (s->slice_first) {  // (only tile sweeps run in parts: every other path settles the request before its first launch)
     TileSlicing* w = s->slice_first;
     s->slice_first = nullptr;
@@ -2456,6 +2527,12 @@ extern "C" int qip_hip_state_apply_ops(qip_hip_state* s, const qip_op* ops, uint
     if (s->n >= K + 4)
       return s->dtype == QIP_C64 ? apply_ops_fused<double>(s, ops, count, K) : apply_ops_fused<float>(s, ops, count, K);
   }
+  if (floor_plan) {
+    TileSchedule sc;
+    if (make_tile_schedule(s->dtype, s->n, ops, count, 1, true, &sc, /*allow_permute=*/false) == QIP_OK && sc.circuit == ops && sc.origin.empty())
+      return s->dtype == QIP_C64 ? apply_ops_floor_plan<double>(s, sc) : apply_ops_floor_plan<float>(s, sc);
+    (void)hipGetLastError();  // (a batch the scheduler rejects goes gate by gate: its failing op is reported there)
+  }
   for (uint64_t i = 0; i < count; ++i) {
     // r5, option "pair_floor" (default 1): a gate whose selectors (controls, the target of a phase-type diagonal) sit inside a
     // 1-KiB wave row sweeps the WHOLE vector for half / a quarter of the algorithmic bytes — the memory system moves whole lines
@@ -2464,30 +2541,19 @@ extern "C" int qip_hip_state_apply_ops(qip_hip_state* s, const qip_op* ops, uint
     // per amplitude, IEEE-equal to the two launches) — the neighbour rides for free.  Everything else stays one launch per gate.
     if (s->pair_floor && i + 1 < count && s->n >= (uint32_t)kPairFloorMinQubits && s->tile_passes && !s->capture_pool && !s->force_generic &&
         !g_force_generic) {
-      // What the two launches move, in sweeps of the whole vector: a gate's algorithmic share, doubled for every selector
-      // inside a wave row (whole lines / rows travel whichever half is needed), at most 1.  One two-item sweep moves 1 (and runs
-      // a little slower than a bare sweep): worth it from 1.3 — T on a low bit + H (1 + 1), CNOT with a low control + anything;
-      // NOT two controlled phases of a QFT (1/4 doubled = 1/2 each: measured 946 -> 986 ms when they were paired).
+      // What the two launches move, in sweeps of the whole vector (floor_share): worth one two-item sweep from 1.3 — T on a low
+      // bit + H (1 + 1), CNOT with a low control + anything.  (Here only where a batch plan does not own the batch, see above.)
       bool floor_gate = false, both = true;
       double moved = 0;
-      const double full = 2.0 * (double)s->amp_bytes * (double)s->namps;
       for (int j = 0; j < 2 && both; ++j) {
         TileItem it;
-        if (classify_tile_item(s->dtype, s->n, &ops[i + j], &it) != QIP_OK || !it.tileable) {
-          both = false;
-          break;
-        }
-        double by = 0;
-        if (qip_hip_op_algorithmic_bytes(s->dtype, s->n, &ops[i + j], &by) != QIP_OK) {
-          both = false;
-          break;
-        }
-        const int in_row = __builtin_popcountll(it.d_mask & 63ull);
-        const double phys = std::min(1.0, by / full * (double)(1u << in_row));
-        if (in_row && phys > by / full) floor_gate = true;
-        moved += phys;
+        double share = 0;
+        bool fg = false;
+        both = classify_tile_item(s->dtype, s->n, &ops[i + j], &it) == QIP_OK && floor_share(s, &ops[i + j], it, &share, &fg);
+        floor_gate = floor_gate || fg;
+        moved += share;
       }
-      if (both && floor_gate && moved >= 1.3) {
+      if (both && floor_gate && moved >= kFloorFuseSweeps) {
         TileSchedule sc;
         if (make_tile_schedule(s->dtype, s->n, &ops[i], 2, 1, true, &sc) == QIP_OK && sc.steps.size() == 1 && sc.steps[0].ops.size() == 2 &&
             sc.steps[0].perm.empty()) {
