@@ -328,10 +328,13 @@ int qip_hip_jit_cache_info(uint64_t* resident, uint64_t* evicted, uint64_t* cap)
  *                        order (exact commutations only, no relabelling, no permutation sweeps) and each step of >= 2 gates
  *                        runs as ONE interpreter sweep when its gates, launched one by one, would move >= 1.3 sweeps of the
  *                        vector (a gate's algorithmic share, doubled per selector inside a 1-KiB wave row, at most 1); every
- *                        other step one launch per gate.  IEEE-equal to one launch per gate; nothing is compiled at run time.
- *                        Batches of a sharded state with a fold / slice request, program recordings, "fuse" >= 2 and a
- *                        relabelled state keep the older rule: a gate whose selectors sit inside a wave row goes with its
- *                        neighbour as one two-item sweep.  0: one launch per gate, always.
+ *                        other step one launch per gate.  An op that launched by itself would run on matrix cores (dense
+ *                        k >= 4; dense k = 3 with two or more targets below bit 6 that does not take the one-op tile sweep:
+ *                        option "single_via_tile" = 0, or more than n - 17 controls) is never fused and no gate is moved past
+ *                        it: it keeps its own launch in circuit order, and its neighbours on either side still fuse.
+ *                        IEEE-equal to one launch per gate, without exception; nothing is compiled at run time.  Batches of a sharded state with a fold / slice request, program recordings,
+ *                        "fuse" >= 2 and a relabelled state keep the older rule (same exclusion): a gate whose selectors sit
+ *                        inside a wave row goes with its neighbour as one two-item sweep.  0: one launch per gate, always.
  */
 int qip_hip_state_set_option(qip_hip_state* s, const char* key, int64_t value);
 

@@ -2442,7 +2442,8 @@ constexpr double kFloorFuseSweeps = 1.3;
 // Option "pair_floor" on the default path (tile = 0): the WHOLE batch planned once as tile sweeps in circuit order (mode 1:
 // exact commutations only, no relabelling, no permutation sweeps — the state never leaves the caller's order) and every step of
 // >= 2 gates that the byte rule accepts launched as ONE interpreter sweep; every other step gate by gate through the gate's own
-// kernel.  The same unfused arithmetic per amplitude as one launch per gate: IEEE-equal (only the sign of a zero may differ).
+// kernel.  An op that launched by itself runs on matrix cores (single_route) was planned as a step of its own that no gate passes.
+// The same unfused arithmetic per amplitude as one launch per gate: IEEE-equal (only the sign of a zero may differ).
 // Interpreter only: nothing is compiled at run time.  A failure leaves a prefix of the (commutation-equivalent) circuit applied
 // in the caller's order, as gate by gate does, and names the caller's op indices (the plan's circuit IS the caller's array).
 template <typename T>
@@ -2528,8 +2529,12 @@ extern "C" int qip_hip_state_apply_ops(qip_hip_state* s, const qip_op* ops, uint
       return s->dtype == QIP_C64 ? apply_ops_fused<double>(s, ops, count, K) : apply_ops_fused<float>(s, ops, count, K);
   }
   if (floor_plan) {
+    // an op that runs on matrix cores by itself is no tile item here (in a sweep it would be the register fold, not its fma chain)
+    // and no gate overtakes it (its three-product forms do not commute exactly with S or Y on other bits)
+    std::vector<char> alone(count);
+    for (uint64_t i = 0; i < count; ++i) alone[i] = single_route(s, &ops[i]) == SingleRoute::kMatrixCores;
     TileSchedule sc;
-    if (make_tile_schedule(s->dtype, s->n, ops, count, 1, true, &sc, /*allow_permute=*/false) == QIP_OK && sc.circuit == ops && sc.origin.empty())
+    if (make_tile_schedule(s->dtype, s->n, ops, count, 1, true, &sc, /*allow_permute=*/false, &alone) == QIP_OK && sc.circuit == ops && sc.origin.empty())
       return s->dtype == QIP_C64 ? apply_ops_floor_plan<double>(s, sc) : apply_ops_floor_plan<float>(s, sc);
     (void)hipGetLastError();  // (a batch the scheduler rejects goes gate by gate: its failing op is reported there)
   }
@@ -2549,7 +2554,8 @@ extern "C" int qip_hip_state_apply_ops(qip_hip_state* s, const qip_op* ops, uint
         TileItem it;
         double share = 0;
         bool fg = false;
-        both = classify_tile_item(s->dtype, s->n, &ops[i + j], &it) == QIP_OK && floor_share(s, &ops[i + j], it, &share, &fg);
+        both = classify_tile_item(s->dtype, s->n, &ops[i + j], &it) == QIP_OK && floor_share(s, &ops[i + j], it, &share, &fg) &&
+               single_route(s, &ops[i + j]) != SingleRoute::kMatrixCores;
         floor_gate = floor_gate || fg;
         moved += share;
       }

@@ -295,6 +295,11 @@ Ins make_ins(std::vector<uint32_t> positions, uint64_t ormask);
 int arena_upload(qip_hip_state* s, const void* src, size_t bytes, size_t arena_off);
 int launch_permute(qip_hip_state* s, const uint32_t* pi_in);
 template <typename T> int apply_op_t(qip_hip_state* s, const qip_op* op);
+// How apply_op_t runs `op` by itself: a one-op tile sweep (the unfused register fold), matrix cores (launch_kq's fma chains and
+// three-product forms), or the op's own kernel.  Option pair_floor's batch plan fuses no op that runs on matrix cores alone, and moves no gate past one
+// (its bits would change).
+enum class SingleRoute { kOwnKernel, kTileSweep, kMatrixCores };
+SingleRoute single_route(const qip_hip_state* s, const qip_op* op);
 template <typename T>
 int launch_gather(qip_hip_state* s, const FlatOp& f, const amp_t<T>* in, uint64_t in_len, amp_t<T>* out, uint64_t out_len,
                   uint64_t in_off, uint64_t out_off, int accumulate);

@@ -976,44 +976,43 @@ static int launch_dense_small(qip_hip_state* s, const Plan& p, bool* done) {
   return QIP_OK;
 }
 
+// launch_kq's choice for a dense k-qubit op: matrix cores (f64 and f32 forms) always for k = 5 (no register form) and k = 6..10
+// (k_gate_big_mfma / k_gate_huge_mfma), and for k = 3, 4 when two or more targets are low bit positions, where the MFMA mapping
+// keeps 64-B+ runs per lane group and the per-lane register form does not (measured at n = 30: profiles/r01_ops_table*.md).
+// r4: k = 4 always where the LDS-staged form can run (a state of >= 17 qubits): the bit-exact VALU fold of a dense 16 x 16
+// gate is 128 unfused f64 operations per amplitude = 3.5 ms of vector issue at n = 30 on top of the HBM time (65.8 % whatever
+// the targets), the matrix-core form through the tile streams whole (split) rows: 75 - 81 % (profiles/r04_ops_table.md).
+// Option mfma = 0 keeps the bit-exact VALU form.
+static bool kq_on_matrix_cores(const qip_hip_state* s, const Plan& p) {
+  const uint32_t k = (uint32_t)p.opos.size();
+  const uint32_t used = (uint32_t)(p.opos.size() + p.cpos.size());
+  if (!s->mfma || s->n < used + 4) return false;
+  if (k > kMaxMfmaK) return k <= kMaxHugeK;
+  uint32_t low_targets = 0;
+  for (uint32_t t : p.opos) low_targets += t < 6;
+  const bool want_mfma = k == 5 || (k >= 3 && low_targets >= 2) || s->mfma == 2 ||  // 2 = force (tuning aid)
+                         (k == 4 && s->n >= (uint32_t)kTileBits + 6 && !g_force_k4_direct);
+  return want_mfma && k >= 3;
+}
+
 template <typename T>
 static int launch_kq(qip_hip_state* s, const Plan& p, amp_t<T>* st, int* actual_cls, const FlatOp& f) {
   const uint32_t k = (uint32_t)p.opos.size();
-  const uint32_t used = (uint32_t)(p.opos.size() + p.cpos.size());
-  // how many target bits sit inside the lane index (a lane's 2^k accesses then share 1-KiB rows
-  // with its neighbours only partially)
-  uint32_t low_targets = 0, min_target = 64;
-  for (uint32_t t : p.opos) {
-    if (t < 6) ++low_targets;
-    min_target = std::min(min_target, t);
-  }
-  {
-    // matrix cores (f64 and f32 forms): always for k = 5 (no register form), and for k = 3, 4 when two or more targets
-    // are low bit positions, where the MFMA mapping keeps 64-B+ runs per lane group and the per-lane
-    // register form does not (measured at n = 30: profiles/r01_ops_table*.md)
-    // r4: k = 4 always where the LDS-staged form can run (a state of >= 17 qubits): the bit-exact VALU fold of a dense 16 x 16
-    // gate is 128 unfused f64 operations per amplitude = 3.5 ms of vector issue at n = 30 on top of the HBM time (65.8 % whatever
-    // the targets), the matrix-core form through the tile streams whole (split) rows: 75 - 81 % (profiles/r04_ops_table.md).
-    // Option mfma = 0 keeps the bit-exact VALU form.
-    const bool want_mfma = k == 5 || (k >= 3 && low_targets >= 2) || s->mfma == 2 ||  // 2 = force (tuning aid)
-                           (k == 4 && s->n >= (uint32_t)kTileBits + 6 && !g_force_k4_direct);
-    if (s->mfma && want_mfma && k >= 3 && k <= kMaxMfmaK && s->n >= used + 4) {
-      *actual_cls = KC_GATE_KQ_MFMA;
-      if ((k == 4 || k == 5) && s->unroll == 0 && !g_force_k4_direct) {  // operands through an LDS-resident tile: whole rows on both global sides
-        bool done = false;
-        QCHK(launch_tile_mfma<T>(s, p, st, &done));
-        if (done) return QIP_OK;
-      }
-      return launch_kq_mfma<T>(s, p, st);
+  // (the lowest target: a lane's 2^k accesses share 1-KiB rows with its neighbours only partially below bit 6)
+  uint32_t min_target = 64;
+  for (uint32_t t : p.opos) min_target = std::min(min_target, t);
+  if (kq_on_matrix_cores(s, p)) {
+    if (k > kMaxMfmaK) {
+      *actual_cls = KC_GATE_KQ_BIG;
+      return k <= kMaxBigK ? launch_big_mfma<T>(s, p, st) : launch_huge_mfma<T>(s, p, st);
     }
-  }
-  if (s->mfma && k > kMaxMfmaK && k <= kMaxBigK && s->n >= used + 4) {
-    *actual_cls = KC_GATE_KQ_BIG;
-    return launch_big_mfma<T>(s, p, st);
-  }
-  if (s->mfma && k > kMaxBigK && k <= kMaxHugeK && s->n >= used + 4) {
-    *actual_cls = KC_GATE_KQ_BIG;
-    return launch_huge_mfma<T>(s, p, st);
+    *actual_cls = KC_GATE_KQ_MFMA;
+    if ((k == 4 || k == 5) && s->unroll == 0 && !g_force_k4_direct) {  // operands through an LDS-resident tile: whole rows on both global sides
+      bool done = false;
+      QCHK(launch_tile_mfma<T>(s, p, st, &done));
+      if (done) return QIP_OK;
+    }
+    return launch_kq_mfma<T>(s, p, st);
   }
   if (k > kMaxRegK && s->mfma && f.distinct) {  // a state too small for the matrix-core kernels: the small dense kernel (1e-12 bar, like them)
     bool done = false;
@@ -1467,6 +1466,49 @@ extern "C" const char* qip_hip_debug_sparse_tile(int dtype, uint32_t n, const qi
   }
 }
 
+// How apply_op_t runs an op by itself, decided in one place: the launcher follows it, and the batch plan of option pair_floor
+// (qip_circuit.hip) keeps an op that runs on matrix cores out of its fused sweeps — a tile sweep is the unfused register fold,
+// the matrix-core forms are fma chains and three-product forms, so fusing such an op would change its bits — and lets no gate
+// overtake it (a three-product form does not commute exactly with a unit phase, S or Y, on other bits).
+// Uncontrolled dense 2- / 3-qubit gates, and Swap ops with a bit inside a 1-KiB row, run as a one-op TILE SWEEP: it streams
+// whole rows on both sides whatever the target bits are (a lane of k_gate_kq with a target below bit 6 reads 16-byte pieces
+// 64 bytes apart: 59 % of peak for k = 2 on bits 0, 1), its free positions are padded from 11 upwards (the fastest tile
+// shapes measured), and the arithmetic is the unfused register fold of k_gate_kq — IEEE-equal to the dedicated VALU kernel
+// and to the oracle, where the matrix-core form of k = 3 is an fma chain.  Measured at n = 30 (profiles/r03_ops_table.md):
+// k = 2 73 -> 77 % (bits 0, 1: 59 -> 77), k = 3 70 -> 79 % (bits 0-2: 58 -> 78), Swap(1) n-1 <-> 0 75 -> 82 %.
+// Uncontrolled dense single-qubit gates on a position above the rows take the same route (H / X over all targets at n = 30:
+// median 6.53 TB/s against 6.30 for k_gate1q_pair; positions 0..5 keep the cross-lane kernel, 6.5 TB/s).
+// Global option "single_via_tile": 0 = dedicated kernels only, 1 = only when a target lies inside a row, 2 = every dense
+// k = 2, 3 and low-bit swap, 3 (default) = single-qubit gates as well.
+template <typename T>
+static SingleRoute single_route(const qip_hip_state* s, const Plan& p) {
+  if (g_single_via_tile && !s->force_generic && !g_force_generic && s->mfma != 0 && s->unroll == 0 && !s->swap_single && s->tile_passes &&
+      (p.cls == KC_GATE_KQ || p.cls == KC_GATE_KQ_MFMA || p.cls == KC_SWAP_BITS || (p.cls == KC_GATE1Q_PAIR && g_single_via_tile >= 3)) &&
+      // r4: a CONTROLLED dense k = 2, 3 gate takes the sweep as well (controls above the rows come off the grid, controls inside
+      // them are lane predicates): k_gate_kq on low targets ran at 42 - 59 %.  Controlled single-qubit gates and swaps keep
+      // their dedicated half / quarter sweeps.
+      (p.cpos.empty() || ((p.cls == KC_GATE_KQ || p.cls == KC_GATE_KQ_MFMA) && p.opos.size() <= 3)) && s->n >= 17 + (uint32_t)p.cpos.size()) {
+    bool low = false;
+    for (uint32_t t : p.opos) low = low || t < 6;
+    // Complex<f32> (a tile row is 512 B there) has its own switch, "single_via_tile_f32"; measured at n = 30 the sweep is level
+    // with or ahead of the packed dedicated kernels as well (H on the top bit 75 -> 81 %, dense k = 2 77 -> 80 %): same default
+    const int64_t mode = std::is_same<T, double>::value ? g_single_via_tile : std::min<int64_t>(g_single_via_tile, g_single_via_tile_f32);
+    const bool dense23 = p.cls != KC_SWAP_BITS && p.cls != KC_GATE1Q_PAIR && (p.opos.size() == 2 || p.opos.size() == 3);
+    const bool dense1 = p.cls == KC_GATE1Q_PAIR && !low && mode >= 3;
+    if ((dense23 && (low || mode >= 2)) || (p.cls == KC_SWAP_BITS && low) || dense1) return SingleRoute::kTileSweep;
+  }
+  return p.cls == KC_GATE_KQ && kq_on_matrix_cores(s, p) ? SingleRoute::kMatrixCores : SingleRoute::kOwnKernel;
+}
+
+SingleRoute single_route(const qip_hip_state* s, const qip_op* op) {
+  FlatOp f;
+  Plan p;
+  if (flatten_op(s->n, op, false, &f) != QIP_OK || make_plan(s->dtype, s->n, f, s->force_generic || g_force_generic, &p) != QIP_OK) {
+    return SingleRoute::kOwnKernel;  // (an op that does not plan fails where it is launched, with its own message)
+  }
+  return s->dtype == QIP_C64 ? single_route<double>(s, p) : single_route<float>(s, p);
+}
+
 template <typename T>
 int apply_op_t(qip_hip_state* s, const qip_op* op) {
   if (s->jit_prepare) return QIP_OK;  // compiling a program's segment kernels: single ops have nothing to prepare
@@ -1480,34 +1522,10 @@ int apply_op_t(qip_hip_state* s, const qip_op* op) {
     if (s->profile) s->prof_launches[KC_NOOP] += 1;
     return QIP_OK;
   }
-  // Uncontrolled dense 2- / 3-qubit gates, and Swap ops with a bit inside a 1-KiB row, run as a one-op TILE SWEEP: it streams
-  // whole rows on both sides whatever the target bits are (a lane of k_gate_kq with a target below bit 6 reads 16-byte pieces
-  // 64 bytes apart: 59 % of peak for k = 2 on bits 0, 1), its free positions are padded from 11 upwards (the fastest tile
-  // shapes measured), and the arithmetic is the unfused register fold of k_gate_kq — IEEE-equal to the dedicated VALU kernel
-  // and to the oracle, where the matrix-core form of k = 3 is an fma chain.  Measured at n = 30 (profiles/r03_ops_table.md):
-  // k = 2 73 -> 77 % (bits 0, 1: 59 -> 77), k = 3 70 -> 79 % (bits 0-2: 58 -> 78), Swap(1) n-1 <-> 0 75 -> 82 %.
-  // Uncontrolled dense single-qubit gates on a position above the rows take the same route (H / X over all targets at n = 30:
-  // median 6.53 TB/s against 6.30 for k_gate1q_pair; positions 0..5 keep the cross-lane kernel, 6.5 TB/s).
-  // Global option "single_via_tile": 0 = dedicated kernels only, 1 = only when a target lies inside a row, 2 = every dense
-  // k = 2, 3 and low-bit swap, 3 (default) = single-qubit gates as well.
-  if (g_single_via_tile && !s->force_generic && !g_force_generic && s->mfma != 0 && s->unroll == 0 && !s->swap_single &&
-      (p.cls == KC_GATE_KQ || p.cls == KC_GATE_KQ_MFMA || p.cls == KC_SWAP_BITS || (p.cls == KC_GATE1Q_PAIR && g_single_via_tile >= 3)) &&
-      // r4: a CONTROLLED dense k = 2, 3 gate takes the sweep as well (controls above the rows come off the grid, controls inside
-      // them are lane predicates): k_gate_kq on low targets ran at 42 - 59 %.  Controlled single-qubit gates and swaps keep
-      // their dedicated half / quarter sweeps.
-      (p.cpos.empty() || ((p.cls == KC_GATE_KQ || p.cls == KC_GATE_KQ_MFMA) && p.opos.size() <= 3)) && s->n >= 17 + (uint32_t)p.cpos.size()) {
-    bool low = false;
-    for (uint32_t t : p.opos) low = low || t < 6;
-    // Complex<f32> (a tile row is 512 B there) has its own switch, "single_via_tile_f32"; measured at n = 30 the sweep is level
-    // with or ahead of the packed dedicated kernels as well (H on the top bit 75 -> 81 %, dense k = 2 77 -> 80 %): same default
-    const int64_t mode = std::is_same<T, double>::value ? g_single_via_tile : std::min<int64_t>(g_single_via_tile, g_single_via_tile_f32);
-    const bool dense23 = p.cls != KC_SWAP_BITS && p.cls != KC_GATE1Q_PAIR && (p.opos.size() == 2 || p.opos.size() == 3);
-    const bool dense1 = p.cls == KC_GATE1Q_PAIR && !low && mode >= 3;
-    if ((dense23 && (low || mode >= 2)) || (p.cls == KC_SWAP_BITS && low) || dense1) {
-      bool done = false;
-      QCHK(tile_apply_single<T>(s, op, &done, p.alg_bytes));
-      if (done) return QIP_OK;
-    }
+  if (single_route<T>(s, p) == SingleRoute::kTileSweep) {
+    bool done = false;
+    QCHK(tile_apply_single<T>(s, op, &done, p.alg_bytes));
+    if (done) return QIP_OK;
   }
   ProfRec rec;
   rec.cls = p.cls;

@@ -118,5 +118,7 @@ int classify_tile_item(int dtype, uint32_t n, const qip_op* op, TileItem* it);
 template <typename T>
 int build_tile_segment(uint32_t n, bool passes, const std::vector<const TileItem*>& seg, std::vector<uint32_t> high, TileSegmentPlan<T>* out,
                        int order_rule = 0, uint32_t p5_override = 0);  // p5_override: 5 / 11 = this tile's sixth low position (one-op sweeps choose)  // order_rule: 0 = gates in the given order, 1 / 2 = fewest passes under tile = 1 / 2's commutation rule
+// alone: per op, 1 = not a tile item whatever it is and no op overtakes it (a step of its own; plans without relabelling, mode
+// bit 2 off)
 int make_tile_schedule(int dtype, uint32_t n, const qip_op* ops, uint64_t count, int mode, bool allow_2q, TileSchedule* out,
-                       bool allow_permute = true);
+                       bool allow_permute = true, const std::vector<char>* alone = nullptr);

@@ -1049,7 +1049,7 @@ static std::vector<uint32_t> seg_choose_high(const SegScan& c, uint64_t head, co
 // shared bit both only test it); without `reorder` only when it, or every op it overtakes, is rounding-free.
 int schedule_tiles(int dtype, uint32_t n, const qip_op* ops, uint64_t count, bool reorder,
                           std::vector<TileItem>* items_out, std::vector<TileStep>* steps, bool allow_2q = true,
-                          bool allow_permute = true) {
+                          bool allow_permute = true, const std::vector<char>* alone = nullptr) {
   std::vector<TileItem>& items = *items_out;
   items.assign(count, TileItem());
   for (uint64_t i = 0; i < count; ++i) {
@@ -1059,6 +1059,11 @@ int schedule_tiles(int dtype, uint32_t n, const qip_op* ops, uint64_t count, boo
       return fail(rc, "op %llu: %s", (unsigned long long)i, msg.c_str());
     }
     if (items[i].kind >= 3 && !allow_2q) items[i].tileable = false;  // k_tile_gates has no 2- / 3-qubit form
+    if (alone && (*alone)[i]) {  // no tile item, and nothing overtakes it: it exchanges across every bit as far as the scan knows
+      items[i].tileable = false;
+      items[i].nd_mask = ~0ull;
+      items[i].d_mask = 0;
+    }
   }
   std::vector<char> done(count, 0);
   uint64_t head = 0;
@@ -1364,7 +1369,7 @@ int schedule_tiles_relabel(int dtype, uint32_t n, const qip_op* ops, uint64_t co
 // mode: bits 0-1 = the "tile" option (1 = circuit order, 2 = commuting reorder), bit 2 = relabel the qubits when that
 // shortens the plan, bit 3 = relabel unconditionally
 static int make_tile_schedule_rule(int dtype, uint32_t n, const qip_op* ops, uint64_t count, int mode, bool allow_2q, TileSchedule* out,
-                                   bool allow_permute) {
+                                   bool allow_permute, const std::vector<char>* alone) {
   const bool reorder = (mode & 3) >= 2;
   bool start_identity = true;
   for (uint32_t p = 0; p < out->init_phys.size(); ++p) start_identity = start_identity && out->init_phys[p] == p;
@@ -1388,7 +1393,7 @@ static int make_tile_schedule_rule(int dtype, uint32_t n, const qip_op* ops, uin
   for (uint32_t p = 0; p < n; ++p) out->final_phys[p] = p;
   out->circuit = ops;
   out->count = count;
-  return schedule_tiles(dtype, n, ops, count, reorder, &out->items, &out->steps, allow_2q, allow_permute);
+  return schedule_tiles(dtype, n, ops, count, reorder, &out->items, &out->steps, allow_2q, allow_permute, alone);
 }
 
 // The plan under each rule for claiming a segment's positions (first come / what a position buys, two weights for the
@@ -1396,23 +1401,24 @@ static int make_tile_schedule_rule(int dtype, uint32_t n, const qip_op* ops, uin
 // n = 24 a sweep costs less than the search: first come only.  Global option "tile_sched": 0 = first come only (and the
 // circuit's own gate order inside every segment), 1 = default, 2 = search at every size and in every mode (tests).
 static int make_tile_schedule_inner(int dtype, uint32_t n, const qip_op* ops, uint64_t count, int mode, bool allow_2q, TileSchedule* out,
-                                    bool allow_permute);
+                                    bool allow_permute, const std::vector<char>* alone);
 int make_tile_schedule(int dtype, uint32_t n, const qip_op* ops, uint64_t count, int mode, bool allow_2q, TileSchedule* out,
-                       bool allow_permute) {
+                       bool allow_permute, const std::vector<char>* alone) {
+  if (alone && ((mode & 4) || alone->size() != count)) return fail(QIP_ERR_INVALID, "internal error: ops kept alone need one flag per op and no relabelling");
   // mode bit 4: wide tiles (seven free positions per segment; a state of at least kWideBits + 1 qubits)
   t_tile_high = ((mode & 16) && n > (uint32_t)kWideBits) ? kWideHigh : kTileHigh;
-  const int rc = make_tile_schedule_inner(dtype, n, ops, count, mode, allow_2q, out, allow_permute);
+  const int rc = make_tile_schedule_inner(dtype, n, ops, count, mode, allow_2q, out, allow_permute, alone);
   t_tile_high = kTileHigh;
   return rc;
 }
 static int make_tile_schedule_inner(int dtype, uint32_t n, const qip_op* ops, uint64_t count, int mode, bool allow_2q, TileSchedule* out,
-                                    bool allow_permute) {
+                                    bool allow_permute, const std::vector<char>* alone) {
   // (only where gates may be reordered freely, tile = 2: in the IEEE-equal mode the sweeps are bound by f64 issue, a plan with
   // fewer, heavier sweeps is not faster there — Grover 15 -> 14 sweeps measured 2 % slower — and first come stays)
   const bool search = g_tile_sched != 0 && (n >= 24 || g_tile_sched == 2) && count >= 8 && ((mode & 3) >= 2 || g_tile_sched == 2);  // (2 = always: tests)
   if (!search) {
     t_seg_rule = 0;
-    return make_tile_schedule_rule(dtype, n, ops, count, mode, allow_2q, out, allow_permute);
+    return make_tile_schedule_rule(dtype, n, ops, count, mode, allow_2q, out, allow_permute, alone);
   }
   const std::vector<uint32_t> init = out->init_phys;
   const bool keep = out->keep_layout;
@@ -1423,7 +1429,7 @@ static int make_tile_schedule_inner(int dtype, uint32_t n, const qip_op* ops, ui
     cand.init_phys = init;
     cand.keep_layout = keep;
     t_seg_rule = rule;
-    const int rc = make_tile_schedule_rule(dtype, n, ops, count, mode, allow_2q, &cand, allow_permute);
+    const int rc = make_tile_schedule_rule(dtype, n, ops, count, mode, allow_2q, &cand, allow_permute, alone);
     t_seg_rule = 0;
     QCHK(rc);
     if (!have || cand.steps.size() < best.steps.size()) {

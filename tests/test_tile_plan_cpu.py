@@ -13,7 +13,10 @@ import pytest
 import rustqip_amd as q
 from oracle import qip_oracle as O
 from rustqip_amd import _ffi, circuits
-from rustqip_amd.ops import TILE_BITS, TILE_LANE_BITS, debug_tile_plan
+from rustqip_amd.ops import TILE_BITS, TILE_LANE_BITS, debug_tile_plan, plan_tiles
+
+from fuzz_ops import (DENSE3_CASES, FUZZ_SEEDS, dense3_case, dense3_in_a_multi_gate_step, fused_coverage, fuzz_circuit,  # noqa: F401
+                      fuzz_default_batch, rand_unitary, seeded_default_batch, unit_phase_case)
 
 TILE_LOW, OUTSIDE = 6, 0xFFFFFFFF
 NLANES = 1 << TILE_LANE_BITS
@@ -275,41 +278,6 @@ def replay(n, ops, mode, x, dtype=None):
         done += step["ops"]
     assert sorted(done) == list(range(len(ops)))
     return st, plan
-
-
-def rand_unitary(k, rng):
-    a = rng.standard_normal((1 << k, 1 << k)) + 1j * rng.standard_normal((1 << k, 1 << k))
-    u, _ = np.linalg.qr(a)
-    return u
-
-
-def fuzz_circuit(n, rng, gates):
-    s2 = 0.5 ** 0.5
-    g1 = [[0, 1, 1, 0], [0, -1j, 1j, 0], [1, 0, 0, -1], [s2, s2, s2, -s2], [1, 0, 0, 1j], [1, 0, 0, cmath.rect(1, 0.785)],
-          [cmath.rect(1, -0.35), 0, 0, cmath.rect(1, 0.35)], [1, 1, 0, 1], [0.3 + 0.1j, -0.7j, 0.2, 0.9 - 0.4j]]
-    ops = []
-    for _ in range(gates):
-        perm = [int(v) for v in rng.permutation(n)]
-        shape = int(rng.integers(0, 9))
-        nc = int(rng.integers(0, 5))
-        if shape <= 3:
-            g = q.make_matrix_op([perm[0]], g1[int(rng.integers(0, len(g1)))])
-            ops.append(q.make_control_op(perm[1:1 + nc], g) if nc and rng.integers(0, 2) else g)
-        elif shape == 4:
-            g = q.make_matrix_op([perm[0]], [1, 0, 0, cmath.rect(1, float(rng.uniform(0, 6.28)))])
-            ops.append(q.make_control_op(perm[1:2 + nc], g))
-        elif shape == 5:
-            g = q.make_swap_op([perm[0]], [perm[1]])
-            ops.append(q.make_control_op(perm[2:2 + nc], g) if nc else g)
-        elif shape == 6:
-            g = q.make_matrix_op(perm[:2], rand_unitary(2, rng).ravel())
-            ops.append(q.make_control_op(perm[2:2 + min(nc, 3)], g) if nc else g)
-        elif shape == 7:
-            g = q.make_matrix_op(perm[:3], rand_unitary(3, rng).ravel())  # a pass of its own three bits
-            ops.append(q.make_control_op(perm[3:3 + min(nc, 3)], g) if nc and rng.integers(0, 2) else g)
-        else:
-            ops.append(q.make_swap_op(perm[:2], perm[2:4]))  # not tileable
-    return ops
 
 
 @pytest.fixture(params=[1, 2], ids=["sched_default", "sched_search"])
@@ -811,3 +779,47 @@ def test_sparse_tile_plan_replayed_on_cpu_matches_the_oracle(dtype):
         if name == "five_per_row":
             op = q.make_sparse_matrix_op([2, 15, 8, 0, 9, 5], [[(c, 1.0) for c in range(5)] for _ in range(64)])
         assert debug_sparse_tile(nn, op, code)["applies"] == 0, name
+
+
+# ---- the default path's batch plan (option pair_floor with tile = 0 plans in mode 1): the premises of
+# tests/test_gpu_default_fusion_kinds.py, without a GPU ------------------------------------------------------------------------
+
+@pytest.mark.parametrize("dtype", [_ffi.QIP_C64, _ffi.QIP_C32], ids=["c64", "c32"])
+def test_default_path_premises_of_the_gpu_batches(dtype):
+    # the dense 3-qubit cases: mode 1 plans the whole batch as ONE multi-gate step that holds the dense gate
+    for name, n in DENSE3_CASES:
+        ops, i3, _, mfma_alone = dense3_case(name, n, np.random.default_rng(7))
+        plan = plan_tiles(n, ops, 1, dtype)
+        assert len(plan) == 1 and dense3_in_a_multi_gate_step(plan, i3), (name, plan)
+        assert mfma_alone == (name != "five_controls")
+    # S and Y after a dense 4-qubit gate on other bits: mode 1 moves them past it
+    for n in (22, 23):
+        ops, i4 = unit_phase_case(n, np.random.default_rng(3))
+        assert plan_tiles(n, ops, 1, dtype) == [[0, 1, 3, 4], [i4]]
+    # the fuzzed batches: their multi-gate steps hold every kind, with and without controls, on bits 5, 11 and 12
+    for n in (22, 23):
+        kinds, at = set(), set()
+        for seed in FUZZ_SEEDS[:2]:
+            ops, tags = seeded_default_batch(n, seed)
+            k, a = fused_coverage(plan_tiles(n, ops, 1, dtype), tags)
+            kinds |= k
+            at |= a
+        assert {(k, c) for k in range(5) for c in (False, True)} <= kinds, (n, sorted(kinds))
+        assert {(k, b) for k in range(5) for b in (5, 11, 12)} <= at, (n, sorted(at))
+
+
+@pytest.mark.parametrize("dtype", [_ffi.QIP_C64, _ffi.QIP_C32], ids=["c64", "c32"])
+@pytest.mark.parametrize("n", [17, 18])
+def test_default_path_fuzz_plans_replayed_on_cpu_match_the_oracle(n, dtype):
+    """fuzz_default_batch (every kind, edge bits, identities, zero-entry and real shapes, breakers, now and then more than
+    n - 17 controls) planned in mode 1 as the default path plans it, replayed on the CPU (tile_p5 = 11 / 5 by dtype)"""
+    rng = np.random.default_rng(500 + n + 7 * dtype)
+    ops, tags = fuzz_default_batch(n, rng, 160, dense3_low=True, dense4=True)
+    x = circuits.random_state(n, seed=n + 3)
+    got, plan = replay(n, ops, 1, x, dtype)
+    want = O.apply_ops_in_place(n, ops, x.copy())
+    bar = 1e-12 if dtype == _ffi.QIP_C64 else 1e-5  # (Complex<f32>: the plan ships its matrices rounded to f32)
+    assert np.max(np.abs(got - want)) <= bar * max(1.0, float(np.max(np.abs(want))))
+    multi = [i for st in plan["steps"] if len(st["ops"]) >= 2 for i in st["ops"]]
+    assert len(plan["steps"]) < len(ops)
+    assert any(tags[i][1] > n - 17 and isinstance(tags[i][0], int) for i in multi)  # many-control ops rode in fused sweeps
