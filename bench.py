@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """bench.py — gate-application throughput on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: it prepares the resident state, runs W warm-up and K timed steps,
+writes --dump-outputs and prints the contract line.  --full adds everything else the benchmark measures or checks: the
+parity checks against the CPU oracle, the CPU baseline and the extras (N = 1), the sharded parity check and the sharded
+extras (N > 1).  --no-parity, --no-cpu-baseline, --no-extras and --headline-only trim a --full run.
 
 N > 1 without a torch.distributed environment re-launches itself as N ranks (one per GPU) under
 torch.distributed.run on 127.0.0.1; under an existing launcher (RANK / WORLD_SIZE set) it runs as that rank.
@@ -14,13 +19,17 @@ n = 33 on 8); weak scaling.  value = algorithmic GB/s of the whole job (32 * 2^n
 
 OUTPUT.  The LAST line of stdout is the compact CONTRACT LINE (one JSON object, < 4 KB): metric, value, unit, n_gpus,
 steps, warmup, ms_per_step, dtype, config, roofline, cpu_baseline, parity_ok, a parity summary, and for N > 1 rccl_ranks /
-per_gpu_efficiency / comm.  It is printed as soon as the headline, its parity check and the CPU baseline are done
-(flushed), and printed again as the final line once the extras have run, so a problem in an extras leg cannot cost the
-headline.  Everything else — every parity leg, per-kernel figures, the extras — goes to bench_detail.json beside this
-file (rewritten after every leg).  --dump-outputs DIR also writes the state the last timed step left, as DIR/*.npy
-(dump_outputs), so that two builds can be compared output for output.
+per_gpu_efficiency / comm (cpu_baseline, parity_ok and parity are null in a plain run).  With --full it is printed as soon
+as the headline, its parity check and the CPU baseline are done (flushed), and printed again as the final line once the
+extras have run, so a problem in an extras leg cannot cost the headline.  Everything else — every parity leg,
+per-kernel figures, the extras — goes to bench_detail.json beside this file (rewritten after every leg).  --dump-outputs
+DIR also writes the state the last timed step left, as DIR/*.npy (dump_outputs), so that two builds can be compared
+output for output.
 
-Order of work (N = 1):
+The timed state (N = 1) is the seeded product state of oracle/window_parity.py advanced by the first 32 gates of the timed
+circuit, with or without the checker.
+
+Order of work (N = 1; a plain run does 2 and 4 only):
   1. parity, core   the timed configuration against the CPU ORACLE before anything is timed: seeded product state with
                     pairwise distinct amplitudes; the first 32 gates of the timed circuit and of the configs[1] mix gate
                     by gate — closed sub-cubes of 2^16+ rows vs the oracle's apply_op_overwrite / apply_op_row, a twin
@@ -65,11 +74,14 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--n-local", type=int, default=30, help="qubits per GPU shard (2^n_local amplitudes)")
     ap.add_argument("--gates", type=int, default=256)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the parity checks against the CPU oracle, the CPU baseline and the extras (N = 1), the sharded parity "
+                         "check and the sharded extras (N > 1); without it a run times the headline and nothing else")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the extras")
+    ap.add_argument("--no-parity", action="store_true", help="--full without the parity checks")
     ap.add_argument("--headline-only", action="store_true",
-                    help="N = 1: only the timed headline steps (profiling passes: no parity check, extras or CPU baseline).  "
+                    help="with --full, N = 1: only the timed headline steps (no parity check, extras or CPU baseline).  "
                          "N > 1: headline + rccl_ranks + the sharded parity check on two chunks, no extras (finishes in minutes)")
     ap.add_argument("--cpu-budget-s", type=float, default=20.0)
     ap.add_argument("--budget-s", type=float, default=270.0,
@@ -85,6 +97,8 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        args.no_extras = args.no_parity = args.no_cpu_baseline = True
     return args
 
 
@@ -858,11 +872,11 @@ def main():
             par.core(ops, ops_mixed)
             par.reset_state()
             em.detail["parity"] = par.detail()
-        else:  # same resident state as the checked run (seeded product state), without the oracle comparison
+        else:  # the state par.reset_state() leaves (seeded product state + the 32 gates core() checks), without the oracle comparison
             from oracle import window_parity as W
 
             st.init_basis(0)
-            st.apply_ops(W.product_state_ops(n, seed=n)[0])
+            st.apply_ops(W.product_state_ops(n, seed=n)[0] + ops[:32])
         compiled = st.compile_ops(ops)
         run_step = lambda: st.apply_compiled(compiled)  # noqa: E731
         sync = st.sync
@@ -933,7 +947,8 @@ def main():
             # (aggregate GB/s / G) / single-GPU GB/s at the same shard size, communication included
             res["per_gpu_efficiency"] = value / world / ref["value"]
             res["per_gpu_efficiency_reference"] = ref
-        em.emit(res, "headline (sharded parity check pending)")
+        if not (args.no_parity and args.no_extras):  # (a plain run prints its line once, at the end)
+            em.emit(res, "headline (sharded parity check pending)")
 
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         em.detail["_now"] = "cpu_baseline"

@@ -106,3 +106,15 @@ def test_bench_dump_outputs_flag_and_files(tmp_path):
             dumps.append(index)
         assert np.array_equal(*dumps)
     assert bench.dump_outputs(str(tmp_path / "rank1"), FakeState(), 4, 1.0, 1) == 0 and not (tmp_path / "rank1").exists()
+
+
+def test_bench_plain_run_times_the_headline_alone_and_full_adds_the_rest():
+    """without --full a run skips the parity checks, the CPU baseline and the extras; --full runs them, and the --no-* flags and
+    --headline-only trim it as before"""
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not plain.full and plain.no_parity and plain.no_cpu_baseline and plain.no_extras
+    full = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert full.full and not (full.no_parity or full.no_cpu_baseline or full.no_extras)
+    trimmed = bench.parse_args(["--full", "--no-extras", "--no-cpu-baseline"])
+    assert trimmed.no_extras and trimmed.no_cpu_baseline and not trimmed.no_parity
+    assert bench.parse_args(["--full", "--headline-only"]).headline_only

@@ -290,7 +290,7 @@ def test_bench_fails_when_parity_fails(tmp_path):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "0", "--n-local", "20", "--gates", "64",
-           "--no-extras", "--no-cpu-baseline"]
+           "--full", "--no-extras", "--no-cpu-baseline"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["QIP_BENCH_DETAIL"] = str(tmp_path / "bench_detail.json")
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=dict(env, QIP_BENCH_SABOTAGE_PARITY="1"))
@@ -311,8 +311,9 @@ def test_bench_fails_when_parity_fails(tmp_path):
 
 @pytest.mark.slow
 def test_bench_dump_outputs_are_the_timed_state(O, tmp_path):
-    """bench.py --dump-outputs: the sampled amplitudes are those of the state the warm-up + timed steps left (the seeded
-    product state, then the timed circuit W + K times), against the oracle on the same inputs; --steps sets the timed steps."""
+    """bench.py --dump-outputs in a plain run (no --full): the sampled amplitudes are those of the state the warm-up + timed
+    steps left (the seeded product state advanced by the first 32 gates of the timed circuit, then the timed circuit W + K
+    times), against the oracle on the same inputs; --steps sets the timed steps; no parity check, CPU baseline or extras run."""
     import json
     import os
     import subprocess
@@ -324,13 +325,17 @@ def test_bench_dump_outputs_are_the_timed_state(O, tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = tmp_path / "dump"
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--n-local", str(n),
-           "--gates", str(gates), "--headline-only", "--dump-outputs", str(out)]
+           "--gates", str(gates), "--dump-outputs", str(out)]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["QIP_BENCH_DETAIL"] = str(tmp_path / "bench_detail.json")
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root, env=env)
     assert res.returncode == 0, res.stderr[-2000:]
     line = json.loads(res.stdout.rstrip().splitlines()[-1])
-    assert line["steps"] == steps and line["ms_per_step"] > 0
+    assert line["steps"] == steps and line["ms_per_step"] > 0 and line["stage"] == "final"
+    assert line["parity_ok"] is None and line["parity"] is None and line["cpu_baseline"] is None and "extras_skipped" not in line
+    assert [l for l in res.stdout.splitlines() if l.startswith("{")] == [res.stdout.rstrip().splitlines()[-1]]  # (one line)
+    detail = json.load(open(tmp_path / "bench_detail.json"))
+    assert detail["parity"] is None and not {"extras", "extras_skipped", "cpu_baseline_detail"} & set(detail), sorted(detail)
     state, index, norm = (np.load(out / f"{k}.npy") for k in ("state", "state_index", "norm_sqr"))
     assert state.dtype == index.dtype == norm.dtype == np.float64 and state.shape == (index.size, 2)
     assert sum(a.nbytes for a in (state, index, norm)) <= 64 << 20
@@ -338,8 +343,8 @@ def test_bench_dump_outputs_are_the_timed_state(O, tmp_path):
     assert np.array_equal(idx, np.unique(idx)) and idx[-1] < (1 << n) and idx.size > (1 << 19)
     x = np.zeros(1 << n, dtype=np.complex128)
     x[0] = 1
-    x = O.apply_ops_in_place(n, W.product_state_ops(n, seed=n)[0], x)  # (returns the result: it ping-pongs two buffers)
     ops = circuits.c2_random_circuit(n, gates, seed=28, single_only=True)
+    x = O.apply_ops_in_place(n, W.product_state_ops(n, seed=n)[0] + ops[:32], x)  # (returns the result: it ping-pongs two buffers)
     for _ in range(warmup + steps):
         x = O.apply_ops_in_place(n, ops, x)
     assert np.max(np.abs(state[:, 0] + 1j * state[:, 1] - x[idx])) <= 1e-12

@@ -52,7 +52,7 @@ def test_bench_multi_rank_code_path_on_one_gpu():
 
     detail_path = os.path.join(tempfile.mkdtemp(), "bench_detail.json")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--n-local", "20", "--gates", "64", "--dist-overlap", "4", "--budget-s", "800"]
+           "--n-local", "20", "--gates", "64", "--dist-overlap", "4", "--budget-s", "800", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root,
                          env=dict(env, QIP_BENCH_DIST_BACKEND="gloo", QIP_BENCH_DETAIL=detail_path))

@@ -14,7 +14,7 @@ if [ "$2" = "final" ]; then
   echo "rc=$?" >> $O/gpu_tests.txt
   tail -n 22 $O/gpu_tests.txt
   export QIP_BENCH_DETAIL=$O/bench_detail.json
-  ( time timeout 900 python bench.py --steps 20 --warmup 5 ) > $O/bench_n1.json 2> $O/bench_n1.err
+  ( time timeout 900 python bench.py --steps 20 --warmup 5 --full ) > $O/bench_n1.json 2> $O/bench_n1.err
   tail -n 1 $O/bench_n1.json | cut -c1-300
   grep -v amdgpu.ids $O/bench_n1.err | tail -n 6
   python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -n 2
@@ -23,7 +23,7 @@ fi
 if [ "$2" = "extras" ]; then
   QIP_BENCH_DETAIL=$O/bench_detail_n33.json timeout 900 python bench.py --headline-only --n-local 33 --gates 64 --steps 2 --warmup 1 > $O/bench_n33.json 2> $O/bench_n33.err
   tail -n 1 $O/bench_n33.json | cut -c1-400
-  QIP_BENCH_DETAIL=$O/bench_detail_2ranks_n29.json QIP_BENCH_DIST_BACKEND=gloo timeout 900 python bench.py --gpus 2 --n-local 29 --steps 2 --warmup 1 --headline-only > $O/bench_2ranks_one_gpu_n29.json 2> $O/bench_2ranks_one_gpu_n29.err
+  QIP_BENCH_DETAIL=$O/bench_detail_2ranks_n29.json QIP_BENCH_DIST_BACKEND=gloo timeout 900 python bench.py --gpus 2 --n-local 29 --steps 2 --warmup 1 --full --headline-only > $O/bench_2ranks_one_gpu_n29.json 2> $O/bench_2ranks_one_gpu_n29.err
   tail -n 1 $O/bench_2ranks_one_gpu_n29.json | cut -c1-400
   timeout 600 python tools/bench_small_n.py > $O/small_n_launch_bound.md 2> $O/small_n.err
   tail -n 8 $O/small_n_launch_bound.md | cut -c1-200
@@ -35,9 +35,9 @@ if [ "$2" != "quick" ]; then
   timeout 1800 python -m pytest tests -m gpu -q --durations=10 > $O/gpu_tests.txt 2>&1
   tail -18 $O/gpu_tests.txt
 fi
-QIP_BENCH_DETAIL=$O/bench_detail.json timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err
+QIP_BENCH_DETAIL=$O/bench_detail.json timeout 900 python bench.py --steps 20 --warmup 5 --full > $O/bench_n1.json 2> $O/bench_n1.err
 echo "bench rc=$?"; tail -2 $O/bench_n1.err
-QIP_BENCH_DETAIL=$O/bench_detail_2ranks.json QIP_BENCH_DIST_BACKEND=gloo timeout 600 python bench.py --gpus 2 --n-local 24 --steps 3 --warmup 1 > $O/bench_2ranks_one_gpu.json 2> $O/bench_2ranks_one_gpu.err
+QIP_BENCH_DETAIL=$O/bench_detail_2ranks.json QIP_BENCH_DIST_BACKEND=gloo timeout 600 python bench.py --gpus 2 --n-local 24 --steps 3 --warmup 1 --full > $O/bench_2ranks_one_gpu.json 2> $O/bench_2ranks_one_gpu.err
 tail -2 $O/bench_2ranks_one_gpu.err
 timeout 600 python tools/bench_ops.py 30 all > $O/ops_table.md 2> $O/ops_table.err
 timeout 600 python tools/bench_ops.py 30 all f32 > $O/ops_table_f32.md 2> $O/ops_table_f32.err

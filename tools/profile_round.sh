@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 sha256sum $R/rustqip_amd/csrc/qip_kernels.h | cut -c1-16 > $O/kernels_sha16.txt   # which kernels these passes describe
-B="python $R/bench.py --no-cpu-baseline --no-parity"
+B="python $R/bench.py --full --no-cpu-baseline --no-parity"
 H="python $R/bench.py --headline-only"
 rocprofv3 --kernel-trace --stats -d $O/prof_stats -o $TAG --output-format csv -- $H --steps 3 --warmup 1 > $O/bench_prof.json 2> $O/bench_prof.err
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/prof_fetch -o $TAG --output-format csv -- $H --steps 1 --warmup 0 > $O/pmc_fetch.json 2> $O/pmc_fetch.err

@@ -61,7 +61,7 @@ def main():
     if len(sys.argv) > 6:  # the same command with every extras leg: per-instantiation table only
         ecsv = glob.glob(os.path.join(sys.argv[6], "*kernel_stats.csv"))[0]
         erows = list(csv.DictReader(open(ecsv)))
-        el = [f"# {tag}: rocprofv3 --kernel-trace --stats of `python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-parity` (extras included)",
+        el = [f"# {tag}: rocprofv3 --kernel-trace --stats of `python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-parity` (extras included)",
               "(tile sweeps: `k_tile_passes` = the interpreter, `qip_segment` = run-time-compiled segments; fusion, QFT, Clifford+T, Grover legs)", "",
               "| kernel | calls | avg ms | total ms | % |", "|---|---|---|---|---|"]
         for r in erows:
