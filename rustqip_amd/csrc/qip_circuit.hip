@@ -110,7 +110,7 @@ static void cluster_apply(Cluster* cl, const std::vector<uint32_t>& pos, const s
 }
 
 template <typename T>
-static int flush_cluster(qip_hip_state* s, const Cluster& cl) {
+static int flush_cluster(qip_hip_state* s, const BatchRun& run, const Cluster& cl) {
   const size_t S = (size_t)1 << cl.pos.size();
   std::vector<uint64_t> idx;
   for (uint32_t p : cl.pos) idx.push_back(s->n - 1 - p);
@@ -125,11 +125,11 @@ static int flush_cluster(qip_hip_state* s, const Cluster& cl) {
   op.n_indices = (uint32_t)idx.size();
   op.indices = idx.data();
   op.dense = data.data();
-  return apply_op_t<T>(s, &op);
+  return apply_op_t<T>(s, &op, run);
 }
 
 template <typename T>
-int apply_ops_fused(qip_hip_state* s, const qip_op* ops, uint64_t count, uint32_t K) {
+int apply_ops_fused(qip_hip_state* s, const BatchRun& run, const qip_op* ops, uint64_t count, uint32_t K) {
   std::vector<Cluster> open;
   auto overlaps = [](const Cluster& c, const std::vector<uint32_t>& pos) {
     for (uint32_t p : pos)
@@ -139,7 +139,7 @@ int apply_ops_fused(qip_hip_state* s, const qip_op* ops, uint64_t count, uint32_
   auto flush_overlapping = [&](const std::vector<uint32_t>& pos) -> int {
     for (size_t i = 0; i < open.size();) {
       if (overlaps(open[i], pos)) {
-        QCHK(flush_cluster<T>(s, open[i]));
+        QCHK(flush_cluster<T>(s, run, open[i]));
         open.erase(open.begin() + i);
       } else {
         ++i;
@@ -161,7 +161,7 @@ int apply_ops_fused(qip_hip_state* s, const qip_op* ops, uint64_t count, uint32_
       std::vector<uint32_t> all;
       for (uint32_t j = 0; j < f.k_all; ++j) all.push_back(s->n - 1 - (uint32_t)f.outer->indices[j]);
       QCHK(flush_overlapping(all));
-      QCHK(apply_op_t<T>(s, &ops[i]));
+      QCHK(apply_op_t<T>(s, &ops[i], run));
       continue;
     }
     std::vector<size_t> hit;
@@ -199,7 +199,7 @@ int apply_ops_fused(qip_hip_state* s, const qip_op* ops, uint64_t count, uint32_
       open.push_back(cl);
     }
   }
-  for (const Cluster& cl : open) QCHK(flush_cluster<T>(s, cl));
+  for (const Cluster& cl : open) QCHK(flush_cluster<T>(s, run, cl));
   return QIP_OK;
 }
 
@@ -1475,7 +1475,9 @@ static int jit_code_locked(const std::string& src, bool fma, std::vector<char>* 
   }
   return QIP_OK;
 }
-static int jit_get_and_launch(qip_hip_state* s, const std::string& src, bool fma, const std::function<int(hipFunction_t)>& launch) {
+// `collect` (a compile-only pass, BatchRun::jit_collect): a miss without `launch` is collected there instead of compiled
+static int jit_get_and_launch(qip_hip_state* s, const std::string& src, bool fma, const std::function<int(hipFunction_t)>& launch,
+                              std::vector<std::pair<std::string, bool>>* collect = nullptr) {
   const std::string key = jit_key(s, src, fma);
   std::lock_guard<std::mutex> lock(g_jit_mutex);
   hipFunction_t fn = nullptr;
@@ -1483,8 +1485,8 @@ static int jit_get_and_launch(qip_hip_state* s, const std::string& src, bool fma
   if (it != g_jit_cache.end()) {
     it->second.last_use = ++g_jit_clock;
     fn = it->second.fn;
-  } else if (!launch && s->jit_collect) {
-    s->jit_collect->push_back({src, fma});  // (the pre-compilation of a plan: jit_compile_collected)
+  } else if (!launch && collect) {
+    collect->push_back({src, fma});  // (the pre-compilation of a plan: jit_compile_collected)
     return QIP_OK;
   } else {
     std::vector<char> code;
@@ -1755,23 +1757,23 @@ static int jit_compile_collected(qip_hip_state* s, std::vector<std::pair<std::st
 }
 
 template <typename T>
-static int launch_tile_segment(qip_hip_state* s, const std::vector<const TileItem*>& seg,
-                               std::vector<uint32_t> high_in, uint32_t p5_override = 0,
-                               const std::vector<uint32_t>* grid_ctl = nullptr, double alg_bytes = 0,
-                               const TileStorePerm* fold = nullptr) {
-  // `fold`: store the tiles into the second buffer, packed for the multi-GPU exchange (TileStorePerm), and make that buffer
-  // current — the remap's gather rides in this sweep's store phase instead of costing a sweep of its own
+static int launch_tile_segment(qip_hip_state* s, const BatchRun& run, const std::vector<const TileItem*>& seg,
+                               std::vector<uint32_t> high_in, const TileStorePerm* fold = nullptr, TileSlicing* sl = nullptr,
+                               uint32_t p5_override = 0, const std::vector<uint32_t>* grid_ctl = nullptr, double alg_bytes = 0) {
+  // `fold` (the batch's last step: BatchRun::fold_request): store the tiles into the second buffer, packed for the multi-GPU
+  // exchange (TileStorePerm), and make that buffer current — the remap's gather rides in this sweep's store phase instead of
+  // costing a sweep of its own.  `sl`: this step's request to run in parts (BatchRun::slice_first / slice_last)
   // `grid_ctl` (one-op sweeps): control positions OUTSIDE the tile that are taken off the grid — only the blocks whose base
   // reads 1 there are launched, so a controlled gate sweeps half / a quarter of the vector like the dedicated kernels do
   // (the kernel's own test of `omask` against the block's base then always passes).  `alg_bytes`: what the profile credits.
   arena_begin_group(s);
   TileSegmentPlan<T> plan;
-  QCHK(build_tile_segment<T>(s->n, s->tile_passes != 0, seg, std::move(high_in), &plan, s->tile >= 2 ? 2 : 1, p5_override));
+  QCHK(build_tile_segment<T>(s->n, s->tile_passes != 0, seg, std::move(high_in), &plan, run.tile >= 2 ? 2 : 1, p5_override));
   const std::vector<uint32_t>& high = plan.high;
   // r5: the interpreter kernel takes runs of diagonal gates as one loop over TileDiagItem steps (tile_merge_diag_runs: the same
   // products in the same order, without the per-gate decoding); the plan itself stays what the generators and the CPU replay read
   TileInterpPlan<T> interp;
-  const bool use_runs = g_tile_diag_runs && s->tile_passes && !s->tile_jit;
+  const bool use_runs = g_tile_diag_runs && s->tile_passes && !run.tile_jit;
   if (use_runs) tile_merge_diag_runs<T>(plan, &interp);
   const bool has_runs = use_runs && interp.runs > 0;
   std::vector<TileGate<T>>& gates = has_runs ? interp.gates : plan.gates;
@@ -1811,14 +1813,12 @@ static int launch_tile_segment(qip_hip_state* s, const std::vector<const TileIte
   // a packed store needs every tile written (no blocks taken off the grid), the pass kernel, rows that stay rows (none of
   // the gathered positions is a lane position of this tile) and the second buffer; otherwise the sweep runs as usual and the
   // remap gathers by itself
-  if (!fold && s->fold_now && s->fold_request && !s->fold_done) fold = s->fold_request;
-  bool folding = fold && fold->g && s->tile_passes && (!grid_ctl || grid_ctl->empty()) && !s->capture_pool && !s->jit_prepare;
+  bool folding = fold && fold->g && s->tile_passes && (!grid_ctl || grid_ctl->empty()) && !s->capture_pool && !run.prepare();
   if (folding)
     for (uint32_t t = 0; t < fold->g; ++t) folding = folding && !tile_is_low(fold->sel[t], plan.p5);
   if (folding) QCHK(ensure_alt(s));
   // r5: the sweep in 2^nbits parts (TileSlicing, qip_internal.h) — the slice positions must be block-index bits of this sweep
   // (not tile positions, not positions taken off the grid), above the rows, and with `need_fold` the store must really be packed
-  TileSlicing* sl = (s->capture_pool || s->jit_prepare) ? nullptr : s->slice_now;
   bool slicing = sl && sl->nbits >= 1 && sl->nbits <= 3 && s->tile_passes && (!grid_ctl || grid_ctl->empty()) && (!sl->need_fold || folding) &&
                  !(sl->in_place_only && folding) && s->n >= (uint32_t)kTileBits + sl->nbits;
   if (slicing)
@@ -1842,11 +1842,10 @@ static int launch_tile_segment(qip_hip_state* s, const std::vector<const TileIte
     return v;
   };
   if (sl && !slicing && sl->fallback) QCHK(sl->fallback());
-  if (sl) s->slice_now = nullptr;  // (consumed: by this step, sliced or not)
   auto folded_swap = [&]() {
     std::swap(s->cur, s->alt);
     std::swap(s->owns_cur, s->owns_alt);
-    s->fold_done = true;
+    if (run.fold_done) *run.fold_done = true;
   };
   const size_t lds = sizeof(amp_t<T>) << kTileBits;
   const TileGate<T>* dg = nullptr;  // device addresses: valid only after the upload (the arena may grow / move)
@@ -1862,16 +1861,16 @@ static int launch_tile_segment(qip_hip_state* s, const std::vector<const TileIte
     if (s->profile) QCHK(prof_begin(s, KC_TILE_GATES, sweep_bytes, &rec));
     return QIP_OK;
   };
-  if (s->tile_passes && s->tile_jit) {
+  if (s->tile_passes && run.tile_jit) {
     // the segment as its own kernel: nothing to upload, the descriptors are constants of the code
-    const bool fma = s->tile_fma && s->tile >= 2;  // tile = 1 promises IEEE equality with the gate-by-gate path: never fused
+    const bool fma = s->tile_fma && run.tile >= 2;  // tile = 1 promises IEEE equality with the gate-by-gate path: never fused
     // structure compiled, numbers in the arena (see tile_jit_source): the default form.  tile_jit = 3 (tuning aid) writes the
     // numbers into the source as literals instead: every constant then occupies vector registers (gfx950's VOP3 takes no
     // 64-bit literal), which makes the configs[1] segments spill under the five-blocks-per-CU register bound (104 vs 90 ms),
     // and every new angle is a new kernel; its one merit is ~3 % fewer multiplies in QFT where equal constants fold
-    const bool parametrised = s->tile_jit != 3;
+    const bool parametrised = run.tile_jit != 3;
     std::vector<T> params;
-    const bool merge = s->tile_merge && s->tile >= 2;  // products of runs of diagonal gates: rounding differs (1e-12 mode only)
+    const bool merge = s->tile_merge && run.tile >= 2;  // products of runs of diagonal gates: rounding differs (1e-12 mode only)
     int remap = ntiles % 64 == 0 ? (int)g_tile_remap : 0;
     if (remap == 4) {  // XCD-aware: tile-number bit J is the first free position at or above 16 (see tile_jit_source)
       uint32_t nb = 0, J = 0;
@@ -1890,8 +1889,8 @@ static int launch_tile_segment(qip_hip_state* s, const std::vector<const TileIte
     if (slicing) remap = 0;
     const std::string src = tile_jit_source<T>(plan, slicing ? ins_sliced : ins, use_nt(s), remap, parametrised ? &params : nullptr, merge,
                                                folding ? fold : nullptr, slicing);
-    QCHK(jit_get_and_launch(s, src, fma, nullptr));  // compile on a miss BEFORE the timed region starts
-    if (s->jit_prepare) return QIP_OK;
+    QCHK(jit_get_and_launch(s, src, fma, nullptr, run.jit_collect));  // compile on a miss BEFORE the timed region starts
+    if (run.prepare()) return QIP_OK;
     if (parametrised && !params.empty()) QCHK(arena_upload(s, params.data(), params.size() * sizeof(T), 0));
     if (s->profile) QCHK(prof_begin(s, KC_TILE_GATES, sweep_bytes, &rec));
     void* st_ptr = s->cur;
@@ -1919,7 +1918,7 @@ static int launch_tile_segment(qip_hip_state* s, const std::vector<const TileIte
     if (folding) folded_swap();
     return QIP_OK;
   }
-  if (s->jit_prepare) return QIP_OK;
+  if (run.prepare()) return QIP_OK;
   if (s->tile_passes) {
     QCHK(begin());
     const uint64_t ntiles_part = ntiles >> (slicing ? sl->nbits : 0);
@@ -1967,24 +1966,23 @@ static int launch_tile_segment(qip_hip_state* s, const std::vector<const TileIte
 
 // a multi-gate step of a wide plan (option "tile_wide"): always its own run-time-compiled kernel
 template <typename T>
-static int launch_wide_segment(qip_hip_state* s, const std::vector<const TileItem*>& seg, std::vector<uint32_t> high_in) {
+static int launch_wide_segment(qip_hip_state* s, const BatchRun& run, const std::vector<const TileItem*>& seg, std::vector<uint32_t> high_in,
+                               const TileStorePerm* fold = nullptr, TileSlicing* sl = nullptr) {
   arena_begin_group(s);
   WidePlan<T> plan;
-  QCHK(build_wide_segment<T>(s->n, seg, std::move(high_in), &plan, s->tile >= 2 ? 2 : 1));
+  QCHK(build_wide_segment<T>(s->n, seg, std::move(high_in), &plan, run.tile >= 2 ? 2 : 1));
   const Ins ins = tile_ins(plan.high, plan.p5);
-  const bool fma = s->tile_fma && s->tile >= 2;
-  const bool parametrised = s->tile_jit != 3;
+  const bool fma = s->tile_fma && run.tile >= 2;
+  const bool parametrised = run.tile_jit != 3;
   std::vector<T> params;
-  const bool merge = s->tile_merge && s->tile >= 2;  // products of runs of diagonal gates: rounding differs (1e-12 mode only)
+  const bool merge = s->tile_merge && run.tile >= 2;  // products of runs of diagonal gates: rounding differs (1e-12 mode only)
   // r5: a packed store (the multi-GPU remap's gather rides in this sweep, TileStorePerm) under the same conditions as the 11-bit
   // sweeps: none of the gathered positions is a lane position of the tile, the second buffer exists
-  const TileStorePerm* fold = (s->fold_now && s->fold_request && !s->fold_done) ? s->fold_request : nullptr;
-  bool folding = fold && fold->g && !s->capture_pool && !s->jit_prepare;
+  bool folding = fold && fold->g && !s->capture_pool && !run.prepare();
   if (folding)
     for (uint32_t t = 0; t < fold->g; ++t) folding = folding && !tile_is_low(fold->sel[t], plan.p5);
   if (folding) QCHK(ensure_alt(s));
   // r5: the sweep in parts (TileSlicing: the sharded state's exchange overlaps with it)
-  TileSlicing* sl = (s->capture_pool || s->jit_prepare) ? nullptr : s->slice_now;
   bool slicing = sl && sl->nbits >= 1 && sl->nbits <= 3 && (!sl->need_fold || folding) && !(sl->in_place_only && folding) &&
                  s->n >= (uint32_t)kWideBits + sl->nbits;
   if (slicing)
@@ -2002,12 +2000,11 @@ static int launch_wide_segment(qip_hip_state* s, const std::vector<const TileIte
     ins_use = make_ins(opened, 0);
   }
   if (sl && !slicing && sl->fallback) QCHK(sl->fallback());
-  if (sl) s->slice_now = nullptr;
   const std::string src = wide_jit_source<T>(plan, ins_use, use_nt(s), parametrised ? &params : nullptr, merge, g_tile_wide_pin != 0, g_tile_wide_dense3_inline != 0, slicing,
                                              folding ? fold : nullptr);
   if (src.empty()) return fail(QIP_ERR_INVALID, "internal: wide segment source");
-  QCHK(jit_get_and_launch(s, src, fma, nullptr));  // compile on a miss before the timed region starts
-  if (s->jit_prepare) return QIP_OK;
+  QCHK(jit_get_and_launch(s, src, fma, nullptr, run.jit_collect));  // compile on a miss before the timed region starts
+  if (run.prepare()) return QIP_OK;
   if (parametrised && !params.empty()) QCHK(arena_upload(s, params.data(), params.size() * sizeof(T), 0));
   ProfRec rec;
   rec.cls = KC_TILE_GATES;
@@ -2045,13 +2042,13 @@ static int launch_wide_segment(qip_hip_state* s, const std::vector<const TileIte
   if (folding) {
     std::swap(s->cur, s->alt);
     std::swap(s->owns_cur, s->owns_alt);
-    s->fold_done = true;
+    if (run.fold_done) *run.fold_done = true;
   }
   return QIP_OK;
 }
 
 template <typename T>
-int tile_apply_single(qip_hip_state* s, const qip_op* op, bool* done, double alg_bytes) {
+int tile_apply_single(qip_hip_state* s, const BatchRun& run, const qip_op* op, const TileStorePerm* fold, bool* done, double alg_bytes) {
   *done = false;
   if (s->n < (uint32_t)kTileBits || !s->tile_passes) return QIP_OK;
   TileItem it;
@@ -2116,16 +2113,14 @@ int tile_apply_single(qip_hip_state* s, const qip_op* op, bool* done, double alg
           hp.push_back(p);
     if (hp.size() != (size_t)kTileHigh) return QIP_OK;
   }
-  const int64_t jit = s->tile_jit;
-  s->tile_jit = 0;  // one op does not repay a run-time compilation: the interpreter kernel (no return between here and the restore)
-  const int rc = launch_tile_segment<T>(s, seg, hp, p5, &grid_ctl, alg_bytes);
-  s->tile_jit = jit;
-  QCHK(rc);
+  BatchRun interp = run;
+  interp.tile_jit = 0;  // one op does not repay a run-time compilation: the interpreter kernel
+  QCHK(launch_tile_segment<T>(s, interp, seg, hp, fold, nullptr, p5, &grid_ctl, alg_bytes));
   *done = true;
   return QIP_OK;
 }
-template int tile_apply_single<double>(qip_hip_state*, const qip_op*, bool*, double);
-template int tile_apply_single<float>(qip_hip_state*, const qip_op*, bool*, double);
+template int tile_apply_single<double>(qip_hip_state*, const BatchRun&, const qip_op*, const TileStorePerm*, bool*, double);
+template int tile_apply_single<float>(qip_hip_state*, const BatchRun&, const qip_op*, const TileStorePerm*, bool*, double);
 
 template <typename T>
 static int debug_jit_t(int dtype, uint32_t n, const qip_op* ops, uint64_t count, int mode, uint64_t* nseg, uint64_t* src_bytes,
@@ -2211,28 +2206,29 @@ constexpr int kAutoJitMinQubits = 22;
 // 7.4 against 6.2 ms); from n = 24 it wins (10.0 against 15.4 ms; n = 26: 36 against 57 ms).
 constexpr int kAutoOneShotMinQubits = 24;
 constexpr int kPairFloorMinQubits = 22;  // option "pair_floor": only where a sweep is HBM-bound (below, launches are)
-static bool tile_wide_of(const qip_hip_state* s) {  // wide tiles: run-time-compiled segments only, a state above one wide tile
+static bool tile_wide_of(const qip_hip_state* s, const BatchRun& run) {  // wide tiles: run-time-compiled segments only, a state above one wide tile
   // (r5: also inside a graph capture — the launch and its parameter upload are ordinary stream work like the 11-bit segments')
-  return s->tile_wide && s->tile_jit && s->tile_passes && s->n > (uint32_t)kWideBits;
+  return run.tile_wide && run.tile_jit && s->tile_passes && s->n > (uint32_t)kWideBits;
 }
-static int tile_mode_of(const qip_hip_state* s) {  // option tile_relabel: 1 = when it shortens the plan, 2 = always
-  return (int)std::min<int64_t>(s->tile, 2) | (s->tile_relabel ? 4 : 0) | (s->tile_relabel == 2 ? 8 : 0) |  // (3 = persistent layout)
-         (tile_wide_of(s) ? 16 : 0);
+static int tile_mode_of(const qip_hip_state* s, const BatchRun& run) {  // option tile_relabel: 1 = when it shortens the plan, 2 = always
+  return (int)std::min<int64_t>(run.tile, 2) | (run.tile_relabel ? 4 : 0) | (run.tile_relabel == 2 ? 8 : 0) |  // (3 = persistent layout)
+         (tile_wide_of(s, run) ? 16 : 0);
 }
 
-int state_tile_mode(const qip_hip_state* s) { return tile_mode_of(s); }  // (qip_dist.hip schedules the edge sweeps of a remap with it)
+// (qip_dist.hip schedules the edge sweeps of a remap with it: what a plain batch on the shard plans with)
+int state_tile_mode(const qip_hip_state* s) { return tile_mode_of(s, BatchRun(*s)); }
 
 template <typename T>
-static int apply_ops_tiled(qip_hip_state* s, const qip_op* ops_in, uint64_t count, bool /*reorder*/) {
+static int apply_ops_tiled(qip_hip_state* s, const qip_op* ops_in, uint64_t count, const BatchRun& run) {
   TileSchedule sc;
   // tile_relabel = 3: the qubit layout persists across calls — the plan starts from the layout the previous call left and
   // does not close with the restoring sweep (that happens once, when somebody needs the caller's order: state_settle).
   // Not inside a graph capture or a compile-only pass: a recorded program must start and end in the caller's order.
-  const bool persist = s->tile_relabel >= 3 && !s->capture_pool && !s->jit_prepare;
+  const bool persist = run.tile_relabel >= 3 && !s->capture_pool && !run.prepare();
   if (!persist && !s->layout.empty()) QCHK(state_settle(s));
   sc.init_phys = s->layout;
   sc.keep_layout = persist;
-  QCHK(make_tile_schedule(s->dtype, s->n, ops_in, count, tile_mode_of(s), s->tile_passes != 0, &sc));
+  QCHK(make_tile_schedule(s->dtype, s->n, ops_in, count, tile_mode_of(s, run), s->tile_passes != 0, &sc));
   {
     // a bit-permutation sweep is out of place: get the second buffer BEFORE the first gate runs; if HBM cannot hold it
     // (a state above half of the 288 GB), fall back to the plan without permutation sweeps instead of failing half way
@@ -2243,12 +2239,12 @@ static int apply_ops_tiled(qip_hip_state* s, const qip_op* ops_in, uint64_t coun
     bool leaves_relabelled = false;
     if (persist)
       for (uint32_t p = 0; p < sc.final_phys.size(); ++p) leaves_relabelled = leaves_relabelled || sc.final_phys[p] != p;
-    if ((permutes || leaves_relabelled) && !s->jit_prepare && !s->alt && ensure_alt(s) != QIP_OK) {
+    if ((permutes || leaves_relabelled) && !run.prepare() && !s->alt && ensure_alt(s) != QIP_OK) {
       (void)hipGetLastError();
       if (!s->layout.empty()) return fail(QIP_ERR_DEVICE, "no room for the second buffer a relabelled state needs");
       sc = TileSchedule();
       // (without relabelling: such a plan neither permutes nor leaves a layout behind)
-      QCHK(make_tile_schedule(s->dtype, s->n, ops_in, count, tile_mode_of(s) & (3 | 16), s->tile_passes != 0, &sc, /*allow_permute=*/false));
+      QCHK(make_tile_schedule(s->dtype, s->n, ops_in, count, tile_mode_of(s, run) & (3 | 16), s->tile_passes != 0, &sc, /*allow_permute=*/false));
     }
   }
   const qip_op* ops = sc.circuit;
@@ -2262,20 +2258,20 @@ static int apply_ops_tiled(qip_hip_state* s, const qip_op* ops_in, uint64_t coun
   // gate-by-gate path: reported, not poisoned.
   bool moves_qubits = !sc.init_phys.empty() || sc.inserted > 0 || sc.absorbed > 0;
   for (const TileStep& st : sc.steps) moves_qubits = moves_qubits || !st.perm.empty();
-  const bool wide = (tile_mode_of(s) & 16) != 0;
+  const bool wide = (tile_mode_of(s, run) & 16) != 0;
   // (the pre-compilation runs BEFORE the layout is cleared — a compiler failure here returns with the handle
   // exactly as it was, still naming the layout the data is in)
   // r5: every segment of the plan that is not resident yet is found FIRST (a compile-only pass that collects the sources), looked
   // up in the disk cache, and the rest compiled side by side in helper processes (jit_compile_collected) before anything runs.
   // A plan that has been through this once is remembered by a fingerprint of its structure, so the steady state (the same
   // circuit applied again and again) does not generate every source twice.
-  if (s->tile_jit && s->tile_passes && !s->capture_pool) {
+  if (run.tile_jit && s->tile_passes && !s->capture_pool) {
     uint64_t fp = 1469598103934665603ull;
     auto mix = [&](uint64_t v) {
       fp ^= v;
       fp *= 1099511628211ull;
     };
-    mix(s->n); mix((uint64_t)s->dtype); mix((uint64_t)s->device); mix((uint64_t)tile_mode_of(s)); mix((uint64_t)s->tile_jit);
+    mix(s->n); mix((uint64_t)s->dtype); mix((uint64_t)s->device); mix((uint64_t)tile_mode_of(s, run)); mix((uint64_t)run.tile_jit);
     mix((uint64_t)(s->tile_fma != 0) | (uint64_t)(s->tile_merge != 0) << 1 | (uint64_t)(g_tile_wide_pin != 0) << 2 |
         (uint64_t)(g_tile_wide_dense3_inline != 0) << 3 | (uint64_t)use_nt(s) << 4 | (uint64_t)g_tile_remap << 8);
     for (const TileStep& st : sc.steps) {
@@ -2295,28 +2291,23 @@ static int apply_ops_tiled(qip_hip_state* s, const qip_op* ops_in, uint64_t coun
     {
       std::lock_guard<std::mutex> lock(g_jit_mutex);
       warm = g_jit_warm_plans.count(fp) != 0 && g_jit_warm_generation == g_jit_generation;
-      if (!warm && s->jit_lookup_only) {  // a plan seen incomplete a moment ago: its segments are still being compiled, do not look again yet
+      if (!warm && run.jit == BatchRun::kLookupOnly) {  // a plan seen incomplete a moment ago: its segments are still being compiled, do not look again yet
         auto it = g_jit_cold_plans.find(fp);
         if (it != g_jit_cold_plans.end() && std::chrono::steady_clock::now() - it->second < std::chrono::milliseconds(1500)) return kJitMiss;
       }
     }
     if (!warm) {
       std::vector<std::pair<std::string, bool>> jobs;
-      const bool outer_prepare = s->jit_prepare;
-      s->jit_collect = &jobs;
-      s->jit_prepare = true;
-      int rc = QIP_OK;
+      BatchRun collect = run;
+      collect.jit = BatchRun::kPrepare;
+      collect.jit_collect = &jobs;
       for (const TileStep& st : sc.steps) {
         if (st.ops.size() < 2 || !st.perm.empty()) continue;
         std::vector<const TileItem*> seg;
         for (uint64_t i : st.ops) seg.push_back(&items[i]);
-        rc = wide ? launch_wide_segment<T>(s, seg, st.high) : launch_tile_segment<T>(s, seg, st.high);
-        if (rc != QIP_OK) break;
+        QCHK(wide ? launch_wide_segment<T>(s, collect, seg, st.high) : launch_tile_segment<T>(s, collect, seg, st.high));
       }
-      s->jit_prepare = outer_prepare;
-      s->jit_collect = nullptr;
-      QCHK(rc);
-      if (s->jit_lookup_only) {
+      if (run.jit == BatchRun::kLookupOnly) {
         std::vector<std::pair<std::string, bool>> misses;
         QCHK(jit_load_only(s, jobs, &misses));
         if (!misses.empty()) {
@@ -2348,29 +2339,26 @@ static int apply_ops_tiled(qip_hip_state* s, const qip_op* ops_in, uint64_t coun
     size_t step_no = 0;
     // a first-step request that no step can take (an empty plan; one step that already serves the last-step request) is settled
     // BEFORE anything is enqueued: its fallback is what makes the data the batch reads complete
-    if (s->slice_first && !s->jit_prepare && !s->capture_pool && (sc.steps.empty() || (sc.steps.size() == 1 && s->slice_last && ends_in_callers_order))) {
-      TileSlicing* w = s->slice_first;
-      s->slice_first = nullptr;
-      if (w->fallback) QCHK(w->fallback());
+    TileSlicing* first = run.slice_first;
+    if (first && !run.prepare() && !s->capture_pool && (sc.steps.empty() || (sc.steps.size() == 1 && run.slice_last && ends_in_callers_order))) {
+      if (first->fallback) QCHK(first->fallback());
+      first = nullptr;
     }
     for (const TileStep& st : sc.steps) {
       ++step_no;
-      s->fold_now = s->fold_request && ends_in_callers_order && step_no == sc.steps.size();  // (the batch's last step may store packed)
+      // (the batch's last step may store packed)
+      const TileStorePerm* fold = ends_in_callers_order && step_no == sc.steps.size() ? run.fold_request : nullptr;
       // r5: the first / last step in parts (the sharded state's overlapped exchange); positions are caller-order positions, so
       // only a plan that starts / ends in the caller's order may take the request.  A step that is not a multi-gate tile sweep
       // (or a sweep that cannot be cut there) consumes it through its fallback.
       TileSlicing* want = nullptr;
-      if (!s->jit_prepare && !s->capture_pool) {
-        if (step_no == sc.steps.size() && s->slice_last && ends_in_callers_order) want = s->slice_last;
-        else if (step_no == 1 && s->slice_first && sc.init_phys.empty() && sc.inserted == 0 && sc.absorbed == 0) want = s->slice_first;
-        else if (step_no == 1 && s->slice_first) {  // (a relabelled plan addresses other positions: settle the request unsliced)
-          TileSlicing* w = s->slice_first;
-          s->slice_first = nullptr;
-          if (w->fallback) QCHK(w->fallback());
-        }
+      if (!run.prepare() && !s->capture_pool) {
+        if (step_no == sc.steps.size() && run.slice_last && ends_in_callers_order) want = run.slice_last;
+        else if (step_no == 1 && first && sc.init_phys.empty() && sc.inserted == 0 && sc.absorbed == 0) want = first;
+        else if (step_no == 1 && first && first->fallback) QCHK(first->fallback());  // (a relabelled plan addresses other positions: settled unsliced)
       }
       TileSlicing dbg;
-      if (!want && g_debug_slice_sweeps >= 2 && !s->jit_prepare && !s->capture_pool && st.perm.empty() && st.ops.size() >= 2) {
+      if (!want && g_debug_slice_sweeps >= 2 && !run.prepare() && !s->capture_pool && st.perm.empty() && st.ops.size() >= 2) {
         // measuring aid (global option "debug_slice_sweeps" = 2 / 4 / 8): EVERY multi-gate sweep in that many parts, cut at the highest
         // index positions its tile leaves alone — what a sliced launch costs by itself, at full size on one GPU, without any exchange
         uint32_t pb = 0;
@@ -2380,35 +2368,22 @@ static int apply_ops_tiled(qip_hip_state* s, const qip_op* ops_in, uint64_t coun
           if (std::find(st.high.begin(), st.high.end(), pp) == st.high.end()) dbg.pos[dbg.nbits++] = pp;
         if (dbg.nbits == pb) want = &dbg;
       }
-      s->slice_now = want;
-      auto unsliced = [&]() -> int {
-        TileSlicing* w = s->slice_now;
-        s->slice_now = nullptr;
-        return (w && w->fallback) ? w->fallback() : QIP_OK;
-      };
-      if (!st.perm.empty()) {  // a run of Swap ops as one bit-permutation sweep
-        if (s->jit_prepare) continue;
-        QCHK(unsliced());
-        QCHK(launch_permute(s, st.perm.data()));
-        continue;
-      }
-      if (st.ops.size() == 1) {
-        QCHK(unsliced());
-        QCHK(apply_op_t<T>(s, &ops[st.ops[0]]));
+      if (!st.perm.empty() || st.ops.size() == 1) {  // not a tile sweep: a request to run in parts is settled unsliced
+        if (want && want->fallback) QCHK(want->fallback());
+        if (st.perm.empty()) QCHK(apply_op_t<T>(s, &ops[st.ops[0]], run, fold));
+        else if (!run.prepare()) QCHK(launch_permute(s, st.perm.data()));  // a run of Swap ops as one bit-permutation sweep
         continue;
       }
       std::vector<const TileItem*> seg;
       for (uint64_t i : st.ops) seg.push_back(&items[i]);
-      if (wide) QCHK(launch_wide_segment<T>(s, seg, st.high));
-      else QCHK(launch_tile_segment<T>(s, seg, st.high));
+      if (wide) QCHK(launch_wide_segment<T>(s, run, seg, st.high, fold, want));
+      else QCHK(launch_tile_segment<T>(s, run, seg, st.high, fold, want));
     }
     return QIP_OK;
   };
   const int rc_steps = run_steps();
-  s->fold_now = false;
-  s->slice_now = nullptr;
   if (rc_steps != QIP_OK) {
-    if (moves_qubits && !s->jit_prepare) {
+    if (moves_qubits && !run.prepare()) {
       s->poisoned = true;
       s->poison_msg = g_last_error;
     }
@@ -2447,9 +2422,9 @@ constexpr double kFloorFuseSweeps = 1.3;
 // Interpreter only: nothing is compiled at run time.  A failure leaves a prefix of the (commutation-equivalent) circuit applied
 // in the caller's order, as gate by gate does, and names the caller's op indices (the plan's circuit IS the caller's array).
 template <typename T>
-static int apply_ops_floor_plan(qip_hip_state* s, const TileSchedule& sc) {
-  const int64_t jit = s->tile_jit;
-  s->tile_jit = 0;  // (launch_tile_segment: the interpreter, whatever the tile options of other paths say)
+static int apply_ops_floor_plan(qip_hip_state* s, const TileSchedule& sc, const BatchRun& run) {
+  BatchRun interp = run;
+  interp.tile_jit = 0;  // (launch_tile_segment: the interpreter, whatever the tile options of other paths say)
   int rc = QIP_OK;
   std::string where;
   for (const TileStep& st : sc.steps) {
@@ -2464,7 +2439,7 @@ static int apply_ops_floor_plan(qip_hip_state* s, const TileSchedule& sc) {
     if (fuse && moved >= kFloorFuseSweeps) {
       std::vector<const TileItem*> seg;
       for (uint64_t i : st.ops) seg.push_back(&sc.items[i]);
-      rc = launch_tile_segment<T>(s, seg, st.high);  // (the profile credits ONE sweep's bytes)
+      rc = launch_tile_segment<T>(s, interp, seg, st.high);  // (the profile credits ONE sweep's bytes)
       if (rc != QIP_OK) {
         for (uint64_t i : st.ops) where += (where.empty() ? "ops " : ", ") + std::to_string(i);
         break;
@@ -2472,7 +2447,7 @@ static int apply_ops_floor_plan(qip_hip_state* s, const TileSchedule& sc) {
       continue;
     }
     for (uint64_t i : st.ops) {
-      rc = apply_op_t<T>(s, &sc.circuit[i]);
+      rc = apply_op_t<T>(s, &sc.circuit[i], interp);
       if (rc != QIP_OK) {
         where = "op " + std::to_string(i);
         break;
@@ -2480,7 +2455,6 @@ static int apply_ops_floor_plan(qip_hip_state* s, const TileSchedule& sc) {
     }
     if (rc != QIP_OK) break;
   }
-  s->tile_jit = jit;
   if (rc != QIP_OK) {
     std::string msg = g_last_error;
     return fail(rc, "%s: %s", where.c_str(), msg.c_str());
@@ -2488,45 +2462,41 @@ static int apply_ops_floor_plan(qip_hip_state* s, const TileSchedule& sc) {
   return QIP_OK;
 }
 
-extern "C" int qip_hip_state_apply_ops(qip_hip_state* s, const qip_op* ops, uint64_t count) try {
+int apply_ops_run(qip_hip_state* s, const qip_op* ops, uint64_t count, const BatchRun& run) try {
   STATE_ENTER_RAW(s);  // (a relabelled state stays relabelled for a relabelling batch: apply_ops_tiled decides)
   if (count && !ops) return fail(QIP_ERR_INVALID, "null op array");
-  if (s->tile >= 1 && !s->force_generic && !g_force_generic && s->n >= (uint32_t)kTileBits) {
+  auto tiled = [s](const qip_op* o, uint64_t c, const BatchRun& r) {
+    return s->dtype == QIP_C64 ? apply_ops_tiled<double>(s, o, c, r) : apply_ops_tiled<float>(s, o, c, r);
+  };
+  if (run.tile >= 1 && !s->force_generic && !g_force_generic && s->n >= (uint32_t)kTileBits) {
     // r6, option "tile_auto" for one-shot callers: the compiled (wide) sweeps when every segment of the plan is already resident
     // or in the disk cache; otherwise the interpreter now, the misses compiled in the background for the next call.  Not for the
     // batches of a sharded state that carry a fold / slice request (their last sweep is chosen by the exchange), not while a
     // program records or pre-compiles (it compiles for itself).
-    if (s->tile_auto && !s->tile_jit && s->tile_passes && s->n >= (uint32_t)kAutoOneShotMinQubits && count >= 2 && !s->capture_pool && !s->jit_prepare &&
-        !s->fold_request && !s->slice_first && !s->slice_last && !s->profile && g_jit_disk) {
-      const int64_t wide0 = s->tile_wide;
-      s->tile_jit = 1;
-      s->tile_wide = s->n > (uint32_t)kWideBits ? 1 : 0;
-      s->jit_lookup_only = true;
-      const int rc = s->dtype == QIP_C64 ? apply_ops_tiled<double>(s, ops, count, s->tile >= 2) : apply_ops_tiled<float>(s, ops, count, s->tile >= 2);
-      s->jit_lookup_only = false;
-      s->tile_jit = 0;
-      s->tile_wide = wide0;
+    if (s->tile_auto && !run.tile_jit && s->tile_passes && s->n >= (uint32_t)kAutoOneShotMinQubits && count >= 2 && !s->capture_pool && !run.prepare() &&
+        !run.fold_request && !run.slice_first && !run.slice_last && !s->profile && g_jit_disk) {
+      BatchRun lookup = run;
+      lookup.tile_jit = 1;
+      lookup.tile_wide = s->n > (uint32_t)kWideBits ? 1 : 0;
+      lookup.jit = BatchRun::kLookupOnly;
+      const int rc = tiled(ops, count, lookup);
       if (rc != kJitMiss) return rc;
     }
-    return s->dtype == QIP_C64 ? apply_ops_tiled<double>(s, ops, count, s->tile >= 2)
-                               : apply_ops_tiled<float>(s, ops, count, s->tile >= 2);
+    return tiled(ops, count, run);
   }
   // The batch plan of option pair_floor owns the batch only where nothing else decides its launches: not for a sharded state's
   // batch that carries a fold / slice request (its last sweep is chosen by the exchange), not while a program records or
   // pre-compiles, not on a state that arrives relabelled, not under force_generic or fuse
   const bool floor_plan = s->pair_floor && count >= 2 && s->n >= (uint32_t)kPairFloorMinQubits && s->tile_passes && !s->capture_pool &&
-                          !s->jit_prepare && !s->force_generic && !g_force_generic && s->fuse < 2 && s->layout.empty() &&
-                          !s->fold_request && !s->slice_first && !s->slice_last;
-  if (s->slice_first) {  // (only tile sweeps run in parts: every other path settles the request before its first launch)
-    TileSlicing* w = s->slice_first;
-    s->slice_first = nullptr;
-    if (w->fallback) QCHK(w->fallback());
-  }
+                          !run.prepare() && !s->force_generic && !g_force_generic && s->fuse < 2 && s->layout.empty() &&
+                          !run.fold_request && !run.slice_first && !run.slice_last;
+  // (only tile sweeps run in parts: every other path settles the request before its first launch)
+  if (run.slice_first && run.slice_first->fallback) QCHK(run.slice_first->fallback());
   if (!s->layout.empty()) QCHK(state_settle(s));
   if (s->fuse >= 2 && !s->force_generic && !g_force_generic) {
     const uint32_t K = (uint32_t)std::min<int64_t>(s->fuse, kMaxMfmaK);  // both precisions have a matrix-core k = 5 kernel
     if (s->n >= K + 4)
-      return s->dtype == QIP_C64 ? apply_ops_fused<double>(s, ops, count, K) : apply_ops_fused<float>(s, ops, count, K);
+      return s->dtype == QIP_C64 ? apply_ops_fused<double>(s, run, ops, count, K) : apply_ops_fused<float>(s, run, ops, count, K);
   }
   if (floor_plan) {
     // an op that runs on matrix cores by itself is no tile item here (in a sweep it would be the register fold, not its fma chain)
@@ -2535,7 +2505,7 @@ extern "C" int qip_hip_state_apply_ops(qip_hip_state* s, const qip_op* ops, uint
     for (uint64_t i = 0; i < count; ++i) alone[i] = single_route(s, &ops[i]) == SingleRoute::kMatrixCores;
     TileSchedule sc;
     if (make_tile_schedule(s->dtype, s->n, ops, count, 1, true, &sc, /*allow_permute=*/false, &alone) == QIP_OK && sc.circuit == ops && sc.origin.empty())
-      return s->dtype == QIP_C64 ? apply_ops_floor_plan<double>(s, sc) : apply_ops_floor_plan<float>(s, sc);
+      return s->dtype == QIP_C64 ? apply_ops_floor_plan<double>(s, sc, run) : apply_ops_floor_plan<float>(s, sc, run);
     (void)hipGetLastError();  // (a batch the scheduler rejects goes gate by gate: its failing op is reported there)
   }
   for (uint64_t i = 0; i < count; ++i) {
@@ -2563,23 +2533,14 @@ extern "C" int qip_hip_state_apply_ops(qip_hip_state* s, const qip_op* ops, uint
         TileSchedule sc;
         if (make_tile_schedule(s->dtype, s->n, &ops[i], 2, 1, true, &sc) == QIP_OK && sc.steps.size() == 1 && sc.steps[0].ops.size() == 2 &&
             sc.steps[0].perm.empty()) {
-          const int64_t tile = s->tile, jit = s->tile_jit, relabel = s->tile_relabel, wide = s->tile_wide;
-          s->tile = 1;
-          s->tile_jit = s->tile_relabel = s->tile_wide = 0;
+          BatchRun pair = run;
+          pair.tile = 1;
+          pair.tile_jit = pair.tile_relabel = pair.tile_wide = 0;
           // the sharded state's requests belong to the BATCH's last step, not to this pair's: a pair in the middle of the batch
           // must not store packed (the gates after it would run on the packed buffer) — only the batch's last two ops may
-          const TileStorePerm* fold_req = s->fold_request;
-          TileSlicing *sf = s->slice_first, *sl = s->slice_last;
-          if (i + 2 < count) s->fold_request = nullptr;
-          s->slice_first = s->slice_last = nullptr;
-          const int rc = s->dtype == QIP_C64 ? apply_ops_tiled<double>(s, &ops[i], 2, false) : apply_ops_tiled<float>(s, &ops[i], 2, false);
-          s->fold_request = fold_req;
-          s->slice_first = sf;
-          s->slice_last = sl;
-          s->tile = tile;
-          s->tile_jit = jit;
-          s->tile_relabel = relabel;
-          s->tile_wide = wide;
+          if (i + 2 < count) pair.fold_request = nullptr;
+          pair.slice_first = pair.slice_last = nullptr;
+          const int rc = tiled(&ops[i], 2, pair);
           if (rc != QIP_OK) {
             std::string msg = g_last_error;
             return fail(rc, "ops %llu, %llu: %s", (unsigned long long)i, (unsigned long long)i + 1, msg.c_str());
@@ -2590,15 +2551,19 @@ extern "C" int qip_hip_state_apply_ops(qip_hip_state* s, const qip_op* ops, uint
         (void)hipGetLastError();
       }
     }
-    s->fold_now = s->fold_request && i + 1 == count;  // (a last op that runs as a one-op tile sweep may store packed)
-    int rc = s->dtype == QIP_C64 ? apply_op_t<double>(s, &ops[i]) : apply_op_t<float>(s, &ops[i]);
-    s->fold_now = false;
+    const TileStorePerm* fold = i + 1 == count ? run.fold_request : nullptr;  // (a last op that runs as a one-op tile sweep may store packed)
+    int rc = s->dtype == QIP_C64 ? apply_op_t<double>(s, &ops[i], run, fold) : apply_op_t<float>(s, &ops[i], run, fold);
     if (rc != QIP_OK) {
       std::string msg = g_last_error;
       return fail(rc, "op %llu: %s", (unsigned long long)i, msg.c_str());
     }
   }
   return QIP_OK;
+} QIP_CATCH_ALL
+
+extern "C" int qip_hip_state_apply_ops(qip_hip_state* s, const qip_op* ops, uint64_t count) try {
+  if (!s) return fail(QIP_ERR_INVALID, "null state handle");
+  return apply_ops_run(s, ops, count, BatchRun(*s));
 } QIP_CATCH_ALL
 
 // ---------------------------------------------------------------------------------------
@@ -2630,24 +2595,15 @@ struct qip_hip_program {
   // results are bit-identical to the interpreter's (tile = 1) / within the mode's own bar (tile = 2).
   bool auto_jit = false, auto_wide = false;
 };
-// the program's own options, in force while one of ITS launches (capture, replay, eager run) is issued
-struct ProgramOptions {
-  qip_hip_state* s;
-  int64_t jit, wide;
-  bool on;
-  explicit ProgramOptions(qip_hip_program* p) : s(p->s), jit(0), wide(0), on(p->s && p->auto_jit) {
-    if (!on) return;
-    jit = s->tile_jit;
-    wide = s->tile_wide;
-    s->tile_jit = 1;
-    s->tile_wide = p->auto_wide ? 1 : 0;
+// the settings ITS launches (capture, replay, eager run) are issued with: the state's options, and the automatic ones
+static BatchRun program_run_of(const qip_hip_program* p) {
+  BatchRun run(*p->s);
+  if (p->auto_jit) {
+    run.tile_jit = 1;
+    run.tile_wide = p->auto_wide ? 1 : 0;
   }
-  ~ProgramOptions() {
-    if (!on) return;
-    s->tile_jit = jit;
-    s->tile_wide = wide;
-  }
-};
+  return run;
+}
 
 static void recording_drop(ProgRecording* r) {
   if (r->exec) (void)hipGraphExecDestroy(r->exec);
@@ -2670,7 +2626,7 @@ void programs_orphan(qip_hip_state* s) {
 // success — only a real descriptor error is returned.
 static int program_capture(qip_hip_program* p, ProgRecording* r) {
   qip_hip_state* s = p->s;
-  ProgramOptions scope(p);
+  const BatchRun run = program_run_of(p);
   recording_drop(r);
   if (s->force_generic || g_force_generic || s->profile) return QIP_OK;
   if (!s->stream) return QIP_OK;  // (the legacy default stream of a wrapped state cannot be captured)
@@ -2687,9 +2643,9 @@ static int program_capture(qip_hip_program* p, ProgRecording* r) {
     if (pl.cls == KC_GATHER_GENERIC && sparse_tile_applies(s, pl, f)) continue;  // (in place through k_sparse_tile)
     out_of_place = pl.cls == KC_GATHER_GENERIC || (pl.cls == KC_GATE_KQ && !reg_or_mfma);
   }
-  if (!out_of_place && s->tile >= 1 && s->n >= (uint32_t)kTileBits) {  // a bit-permutation sweep is out of place too
+  if (!out_of_place && run.tile >= 1 && s->n >= (uint32_t)kTileBits) {  // a bit-permutation sweep is out of place too
     TileSchedule sc;
-    QCHK(make_tile_schedule(s->dtype, s->n, p->ops, p->count, tile_mode_of(s), s->tile_passes != 0, &sc));
+    QCHK(make_tile_schedule(s->dtype, s->n, p->ops, p->count, tile_mode_of(s, run), s->tile_passes != 0, &sc));
     for (const TileStep& st : sc.steps) out_of_place = out_of_place || !st.perm.empty();
   }
   if (out_of_place && !s->alt && ensure_alt(s) != QIP_OK) {
@@ -2697,11 +2653,10 @@ static int program_capture(qip_hip_program* p, ProgRecording* r) {
     p->capture_failed = true;
     return QIP_OK;
   }
-  if (s->tile >= 1 && s->tile_jit) {  // run-time compilation cannot happen inside a stream capture: do it now
-    s->jit_prepare = s->jit_for_capture = true;
-    const int rc = qip_hip_state_apply_ops(s, p->ops, p->count);
-    s->jit_prepare = s->jit_for_capture = false;
-    QCHK(rc);
+  if (run.tile >= 1 && run.tile_jit) {  // run-time compilation cannot happen inside a stream capture: do it now
+    BatchRun prepare = run;
+    prepare.jit = BatchRun::kPrepare;
+    QCHK(apply_ops_run(s, p->ops, p->count, prepare));
   }
   void* const arena0 = s->arena;
   const size_t arena_cap0 = s->arena_cap;
@@ -2729,7 +2684,7 @@ static int program_capture(qip_hip_program* p, ProgRecording* r) {
     }
     s->capture_pool = &pool;
     jit_capture_scope(+1);
-    const int rc = qip_hip_state_apply_ops(s, p->ops, p->count);
+    const int rc = apply_ops_run(s, p->ops, p->count, run);
     s->capture_pool = nullptr;
     hipGraph_t g = nullptr;
     const hipError_t e = hipStreamEndCapture(s->stream, &g);
@@ -2825,10 +2780,10 @@ extern "C" int qip_hip_program_run(qip_hip_program* p) try {
   qip_hip_state* s = p->s;
   if (!s) return fail(QIP_ERR_INVALID, "the state this program was recorded against has been destroyed");
   STATE_ENTER(s);
-  ProgramOptions scope(p);
+  const BatchRun run = program_run_of(p);
   if (s->profile || s->force_generic || g_force_generic) {  // (profiling brackets every kernel with events; the literal kernel is a test route)
     p->last_was_graph = 0;
-    return qip_hip_state_apply_ops(s, p->ops, p->count);
+    return apply_ops_run(s, p->ops, p->count, run);
   }
   for (int attempt = 0; attempt < 2; ++attempt) {
     // the recording made for the buffers as they are now; none yet (the previous run left the state on its other buffer, an eager
@@ -2848,7 +2803,7 @@ extern "C" int qip_hip_program_run(qip_hip_program* p) try {
     bool stale = false;
     {
       std::lock_guard<std::mutex> lock(g_jit_mutex);
-      stale = s->tile_jit && r->jit_gen != g_jit_generation;
+      stale = run.tile_jit && r->jit_gen != g_jit_generation;
       if (!stale) HIPCHK(hipGraphLaunch(r->exec, s->stream));
     }
     if (stale) {
@@ -2863,7 +2818,7 @@ extern "C" int qip_hip_program_run(qip_hip_program* p) try {
     return QIP_OK;
   }
   p->last_was_graph = 0;
-  return qip_hip_state_apply_ops(s, p->ops, p->count);
+  return apply_ops_run(s, p->ops, p->count, run);
 } QIP_CATCH_ALL
 
 extern "C" int qip_hip_program_is_graph(const qip_hip_program* p) try { return p ? p->last_was_graph : 0; } QIP_CATCH_ALL

@@ -999,12 +999,7 @@ static int dist_run_steps(qip_hip_dist* d, std::vector<qipd::Step>& steps) {
   d->agreed_for = (size_t)-1;
   const int rc = dist_run_steps_inner(d, steps);
   // whatever comes next on the shard's stream (a download, a measurement, the next batch) is ordered after the last slices
-  if (rc == QIP_OK) return dist_wait_rx(d);
-  // (the requests point at objects of the failed batch's frame — none may outlive it)
-  d->shard->slice_first = d->shard->slice_last = d->shard->slice_now = nullptr;
-  d->shard->fold_request = nullptr;
-  d->shard->fold_now = d->shard->fold_done = false;
-  return rc;
+  return rc == QIP_OK ? dist_wait_rx(d) : rc;
 }
 static int dist_run_steps_inner(qip_hip_dist* d, std::vector<qipd::Step>& steps) {
   qip_hip_state* s = d->shard;
@@ -1023,8 +1018,10 @@ static int dist_run_steps_inner(qip_hip_dist* d, std::vector<qipd::Step>& steps)
       // phase of this batch's last tile sweep — every sweep writes whole rows anyway, so it writes them to their packed places
       // in the second buffer — and the PACK step is skipped.  Not when a gathered position lies inside a row (the rows would
       // break into 16-byte pieces: the bit-permutation sweep handles that), nor when the batch does not end in a tile sweep.
+      BatchRun run(*s);  // (the batch's requests to the shard)
       TileStorePerm sp;
       memset(&sp, 0, sizeof sp);
+      bool folded = false;
       const bool pack_next = g_dist_fold_pack && jx < steps.size() && steps[jx].kind == qipd::Step::PACK && s->layout.empty();
       if (pack_next) {
         sp.g = g;
@@ -1035,8 +1032,8 @@ static int dist_run_steps_inner(qip_hip_dist* d, std::vector<qipd::Step>& steps)
           sp.sel[t] = steps[jx].sel[t];
           sp.sel_desc[t] = desc[t];
         }
-        s->fold_request = &sp;
-        s->fold_done = false;
+        run.fold_request = &sp;
+        run.fold_done = &folded;
       }
       // r5, option "dist_overlap": the exchange that follows this batch in P slices on the communication stream, slice k sent as
       // soon as the batch's LAST tile sweep — launched in P parts — has stored it; and the slices of the exchange BEFORE this
@@ -1056,7 +1053,7 @@ static int dist_run_steps_inner(qip_hip_dist* d, std::vector<qipd::Step>& steps)
           return QIP_OK;
         };
         sl_post.fallback = [d]() -> int { return dist_wait_rx(d); };
-        s->slice_first = &sl_post;
+        run.slice_first = &sl_post;
       } else {
         QCHK(dist_wait_rx(d));
       }
@@ -1121,14 +1118,9 @@ static int dist_run_steps_inner(qip_hip_dist* d, std::vector<qipd::Step>& steps)
           HIPCHK(hipEventRecord(d->ev_rx[k], d->comm_stream));
           return QIP_OK;
         };
-        s->slice_last = &sl_pre;
+        run.slice_last = &sl_pre;
       }
-      const int rc_batch = qip_hip_state_apply_ops(s, m.flat.data(), m.flat.size());
-      const bool folded = pack_next && s->fold_done;
-      s->fold_request = nullptr;
-      s->fold_done = false;
-      s->slice_first = s->slice_last = s->slice_now = nullptr;
-      QCHK(rc_batch);
+      QCHK(apply_ops_run(s, m.flat.data(), m.flat.size(), run));
       if (post) {
         QCHK(dist_wait_rx(d));  // (a no-op in stream order when the first sweep has awaited every slice; otherwise the safety net)
         if (sl_post.parts_done == P) d->stats.remaps_overlapped_after += 1;

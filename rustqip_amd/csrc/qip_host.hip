@@ -20,7 +20,7 @@ static int apply_op_host_t(int dtype, uint32_t n, const qip_op* op, const void* 
     const bool full = in_off == 0 && out_off == 0 && in_len == N && out_len == N;
     if (full) {
       QCHK(qip_hip_state_upload(s, in, 0, N));
-      QCHK(apply_op_t<T>(s, op));
+      QCHK(apply_op_t<T>(s, op, BatchRun(*s)));
       if (accumulate) {
         QCHK(ensure_alt(s));
         HIPCHK(hipMemcpyAsync(s->alt, out, N * ab, hipMemcpyHostToDevice, s->stream));

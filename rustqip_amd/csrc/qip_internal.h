@@ -177,20 +177,6 @@ struct qip_hip_state {
   // from the amplitudes fails with the original message until init_basis / a full upload / copy_from overwrites them.
   bool poisoned = false;
   std::string poison_msg;
-  // The sharded state's remap (qip_dist.hip) asks the batch it hands to this shard to leave its result PACKED in the second
-  // buffer (TileStorePerm: the leaving qubits' positions gathered on top): the last sweep of the batch — if it is a tile
-  // sweep — stores its tiles there and the remap needs no gather sweep of its own.  `fold_now` is raised while the batch's
-  // last step runs, `fold_done` reports that a sweep took the request.
-  const TileStorePerm* fold_request = nullptr;
-  bool fold_now = false, fold_done = false;
-  // r5: the FIRST / LAST tile sweep of a batch launched in 2^nbits parts, part k = the blocks whose base index reads k at `pos`
-  // (amplitude-index positions that are not tile positions of that sweep) — the sharded state's exchange is cut into the same
-  // slices and overlaps with these sweeps (qip_dist.hip): `after(k)` runs once part k is enqueued (the slice can be sent as soon
-  // as it is stored), `before(k)` before part k is enqueued (it may start as soon as the slice has landed).  `fallback` runs
-  // instead when the step turns out not to be sliceable.  See TileSlicing.
-  struct TileSlicing* slice_first = nullptr;
-  struct TileSlicing* slice_last = nullptr;
-  struct TileSlicing* slice_now = nullptr;
   int64_t swap_single = 0;  // 1 = one sweep per transposition (tuning aid; default groups them, k_swapn)
   int64_t tile_jit = 0;     // 1 (= 2) = tile segments run as kernels compiled at run time for that segment's STRUCTURE (hiprtc,
                             // cached), its numbers are kernel data (angles can change without recompiling); 3 = numbers as literals
@@ -202,13 +188,6 @@ struct qip_hip_state {
   int64_t pair_floor = 1;   // r5: gate-by-gate apply_ops pairs a gate whose selectors sit inside a wave row (a full sweep for half the bytes)
                             // with its neighbour into one two-item tile sweep when both fit a tile (IEEE-equal); 0 = one launch per gate, always
   int num_cus = 256;        // compute units of the device
-  bool jit_prepare = false; // compile the segments' kernels but launch nothing (before a graph capture; the parallel pre-compilation)
-  bool jit_for_capture = false;  // ... on behalf of a graph capture: the plan must be the one the capture will record
-  bool jit_lookup_only = false;  // r6 (option tile_auto, one-shot callers): the plan's segments are only LOOKED UP (memory, disk cache); a miss
-                                 // hands them to background helpers and the batch returns kJitMiss before anything has run
-  // r4: apply_ops collects the sources of a plan's segments that are not in the kernel cache yet (source text, contraction flag)
-  // and compiles them on several host threads before the first launch (hiprtc: ~0.35 s per 11-bit segment, ~1.4 s per wide one)
-  std::vector<std::pair<std::string, bool>>* jit_collect = nullptr;
   // program capture (hipGraph): non-null while a program records its launches.  Op payloads then go to the PROGRAM's own
   // device pool instead of the arena (ProgPool below): the graph holds kernel nodes only and replays nothing from the host.
   struct ProgPool* capture_pool = nullptr;
@@ -242,6 +221,37 @@ struct TileSlicing {
   uint32_t parts_done = 0;
   bool folded = false;
 };
+// The settings of ONE apply_ops batch (apply_ops_run), passed down its call tree as a value: the library never writes the
+// handle's options on a batch's behalf.  The public entry copies the options; programs, the sharded state and the batch's own
+// sub-batches pass modified copies.
+struct BatchRun {
+  int64_t tile = 0, tile_jit = 0, tile_wide = 0, tile_relabel = 0;  // the options of those names, as this batch plans with them
+  // kPrepare: compile the segments' kernels but launch nothing (before a graph capture; the parallel pre-compilation).
+  // kLookupOnly (r6, option tile_auto, one-shot callers): the plan's segments are only LOOKED UP (memory, disk cache); a miss
+  // hands them to background helpers and the batch returns kJitMiss before anything has run.
+  enum Jit { kRun, kPrepare, kLookupOnly } jit = kRun;
+  // r4 (kPrepare): the sources of a plan's segments that are not in the kernel cache yet (source text, contraction flag) are
+  // collected here instead of compiled; apply_ops compiles them on several host threads before the first launch (hiprtc:
+  // ~0.35 s per 11-bit segment, ~1.4 s per wide one)
+  std::vector<std::pair<std::string, bool>>* jit_collect = nullptr;
+  // The sharded state's remap (qip_dist.hip) asks the batch it hands to this shard to leave its result PACKED in the second
+  // buffer (TileStorePerm: the leaving qubits' positions gathered on top): the last sweep of the batch — if it is a tile
+  // sweep — stores its tiles there and the remap needs no gather sweep of its own.  The step loop hands the request to the
+  // launch of the batch's last step only; `*fold_done` is set when a sweep took it.
+  const TileStorePerm* fold_request = nullptr;
+  bool* fold_done = nullptr;
+  // r5: the FIRST / LAST tile sweep of a batch launched in 2^nbits parts, part k = the blocks whose base index reads k at `pos`
+  // (amplitude-index positions that are not tile positions of that sweep) — the sharded state's exchange is cut into the same
+  // slices and overlaps with these sweeps (qip_dist.hip): `after(k)` runs once part k is enqueued (the slice can be sent as soon
+  // as it is stored), `before(k)` before part k is enqueued (it may start as soon as the slice has landed).  `fallback` runs
+  // instead when the step turns out not to be sliceable.  The step loop hands each to the launch of its step.
+  TileSlicing* slice_first = nullptr;
+  TileSlicing* slice_last = nullptr;
+  explicit BatchRun(const qip_hip_state& s) : tile(s.tile), tile_jit(s.tile_jit), tile_wide(s.tile_wide), tile_relabel(s.tile_relabel) {}
+  bool prepare() const { return jit == kPrepare; }
+};
+// qip_circuit.hip: qip_hip_state_apply_ops with explicit settings (the same handle checks)
+int apply_ops_run(qip_hip_state* s, const qip_op* ops, uint64_t count, const BatchRun& run);
 int ensure_arena(qip_hip_state* s, size_t bytes);
 // start of a launch group (one op, one tile segment): while a program records, its payload gets a region of its own
 static inline void arena_begin_group(qip_hip_state* s) {
@@ -257,7 +267,8 @@ int jit_set_cache_cap(int64_t cap);      // qip_circuit.hip (global option "jit_
 int jit_set_disk_cap_mb(int64_t mb);     // qip_circuit.hip (global option "jit_disk_cap_mb")
 uint64_t jit_cache_generation();
 // qip_circuit.hip: `op` as a one-item tile sweep; *done = false when it is not a tile item (nothing launched)
-template <typename T> int tile_apply_single(qip_hip_state* s, const qip_op* op, bool* done, double alg_bytes = 0);
+template <typename T>
+int tile_apply_single(qip_hip_state* s, const BatchRun& run, const qip_op* op, const TileStorePerm* fold, bool* done, double alg_bytes);
 int prof_begin(qip_hip_state* s, int cls, double bytes, ProfRec* r);
 int prof_end(qip_hip_state* s, ProfRec* r);
 int state_settle(qip_hip_state* s);  // qip_launch.hip: a relabelled state back to the caller's order (one permutation sweep)
@@ -294,7 +305,8 @@ static inline unsigned grid_stride(uint64_t items) {
 Ins make_ins(std::vector<uint32_t> positions, uint64_t ormask);
 int arena_upload(qip_hip_state* s, const void* src, size_t bytes, size_t arena_off);
 int launch_permute(qip_hip_state* s, const uint32_t* pi_in);
-template <typename T> int apply_op_t(qip_hip_state* s, const qip_op* op);
+// `fold`: the batch's fold request when `op` is its last step (BatchRun::fold_request); a plain single op passes BatchRun(*s)
+template <typename T> int apply_op_t(qip_hip_state* s, const qip_op* op, const BatchRun& run, const TileStorePerm* fold = nullptr);
 // How apply_op_t runs `op` by itself: a one-op tile sweep (the unfused register fold), matrix cores (launch_kq's fma chains and
 // three-product forms), or the op's own kernel.  Option pair_floor's batch plan fuses no op that runs on matrix cores alone, and moves no gate past one
 // (its bits would change).

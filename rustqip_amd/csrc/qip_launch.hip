@@ -1510,8 +1510,8 @@ SingleRoute single_route(const qip_hip_state* s, const qip_op* op) {
 }
 
 template <typename T>
-int apply_op_t(qip_hip_state* s, const qip_op* op) {
-  if (s->jit_prepare) return QIP_OK;  // compiling a program's segment kernels: single ops have nothing to prepare
+int apply_op_t(qip_hip_state* s, const qip_op* op, const BatchRun& run, const TileStorePerm* fold) {
+  if (run.prepare()) return QIP_OK;  // compiling a program's segment kernels: single ops have nothing to prepare
   (void)hipGetLastError();  // a stale error of an unrelated earlier call must not be blamed on this launch
   arena_begin_group(s);
   FlatOp f;
@@ -1524,7 +1524,7 @@ int apply_op_t(qip_hip_state* s, const qip_op* op) {
   }
   if (single_route<T>(s, p) == SingleRoute::kTileSweep) {
     bool done = false;
-    QCHK(tile_apply_single<T>(s, op, &done, p.alg_bytes));
+    QCHK(tile_apply_single<T>(s, run, op, fold, &done, p.alg_bytes));
     if (done) return QIP_OK;
   }
   ProfRec rec;
@@ -1628,12 +1628,12 @@ int apply_op_t(qip_hip_state* s, const qip_op* op) {
 
 extern "C" int qip_hip_state_apply_op(qip_hip_state* s, const qip_op* op) try {
   STATE_ENTER(s);
-  return s->dtype == QIP_C64 ? apply_op_t<double>(s, op) : apply_op_t<float>(s, op);
+  return s->dtype == QIP_C64 ? apply_op_t<double>(s, op, BatchRun(*s)) : apply_op_t<float>(s, op, BatchRun(*s));
 } QIP_CATCH_ALL
 
 
 // the other translation units call these (qip_internal.h)
-template int apply_op_t<double>(qip_hip_state*, const qip_op*);
-template int apply_op_t<float>(qip_hip_state*, const qip_op*);
+template int apply_op_t<double>(qip_hip_state*, const qip_op*, const BatchRun&, const TileStorePerm*);
+template int apply_op_t<float>(qip_hip_state*, const qip_op*, const BatchRun&, const TileStorePerm*);
 template int launch_gather<double>(qip_hip_state*, const FlatOp&, const amp_t<double>*, uint64_t, amp_t<double>*, uint64_t, uint64_t, uint64_t, int);
 template int launch_gather<float>(qip_hip_state*, const FlatOp&, const amp_t<float>*, uint64_t, amp_t<float>*, uint64_t, uint64_t, uint64_t, int);
