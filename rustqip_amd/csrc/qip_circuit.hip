@@ -818,6 +818,207 @@ template <typename T> static std::string fnum(T v) {
   return r;
 }
 
+// ---- the segment source both tile shapes write alike --------------------------------------------------------------------------
+// A gate as the writers consume it, resolved against its pass: the call it makes and the register-index bits of its targets.
+// SEG_OTHER: the call is the shape's own (the dense 2- and 3-qubit gates: narrow and wide read their matrices differently).
+enum SegCall { SEG_OTHER, SEG_DIAG_UNIFORM, SEG_DIAG_LANE, SEG_DIAG_LANE_CTL, SEG_DIAG_REG, SEG_DENSE, SEG_DENSE_LANE, SEG_SWAP };
+template <typename T> struct SegGate {
+  TileGate<T> g;  // as its literal shows it: cm_reg / cm_lane = its controls on register / lane bits
+  SegCall call = SEG_OTHER;
+  int j[2] = {0, 0};
+};
+
+template <typename T> struct SegWriter {
+  // `params` (option "tile_jit" = 2, see tile_jit_source): every number that is not exactly 0 or +-1 becomes a read of P[k]
+  std::vector<T>* params;
+  std::string o;
+  explicit SegWriter(std::vector<T>* p) : params(p) {}
+  static std::string N(uint64_t v) { return std::to_string(v); }
+  static std::string U(uint64_t v) { return std::to_string(v) + "ull"; }
+  static constexpr const char* kLaneArgs = "g.cm_lane != 0u, (tb & g.cm_lane) == g.cm_lane";  // (the calls with lane controls)
+  void L(const std::string& line) { o += line; o += "\n"; }
+  std::string comp(T v) {
+    if (!params || v == (T)0 || v == (T)1 || v == (T)-1) return fnum<T>(v);  // (a -0 prints as -0.0 and stays one)
+    params->push_back(v);
+    return "P[" + N(params->size() - 1) + "]";
+  }
+  std::string amp(amp_t<T> a) {
+    const std::string re = comp(a.x);  // fixed evaluation order: the parameter numbering is part of the source
+    const std::string im = comp(a.y);
+    return "{" + re + ", " + im + "}";
+  }
+  std::string matrix_literal(const amp_t<T>* m, int cnt) {
+    std::string r = "const A M[" + N(cnt) + "] = {";
+    for (int k = 0; k < cnt; ++k) r += amp(m[k]) + (k + 1 < cnt ? ", " : "}; ");
+    return r;
+  }
+  // a gate's 4x4 / 8x8 matrix: one contiguous block of the parameter array, or literals.  r4: read row by row through a pointer
+  // like the interpreter does (wave-uniform scalar loads as they are needed).  Spelt out as 64 named components, all 128 scalars
+  // of a dense 3-qubit gate were live at once: the dense-k3 Grover segments ran SLOWER compiled than interpreted (108.9 vs 101.4 ms).
+  std::string matrix(const amp_t<T>* m, int cnt) {
+    if (!params) return matrix_literal(m, cnt);
+    if (params->size() & 1) params->push_back((T)0);  // (16-byte alignment of the block for Complex<f64>)
+    const size_t off = params->size();
+    for (int k = 0; k < cnt; ++k) {
+      params->push_back(m[k].x);
+      params->push_back(m[k].y);
+    }
+    return "const A* __restrict__ M = reinterpret_cast<const A*>(P + " + N(off) + "); ";
+  }
+  // includes, tile_base, dst_of (a packed store), the signature and the kernel's first lines up to its shared-memory buffer `buf`
+  void prologue(const Ins& ins, uint32_t p5, const TileStorePerm* fold, const char* bounds, bool sliced, const std::string& buf, bool nt) {
+    L("#include \"qip_kernels.h\"");
+    L("using namespace qipk;");
+    L(std::string("typedef ") + (std::is_same<T, double>::value ? "double" : "float") + " T;");
+    L("typedef amp_t<T> A;");
+    // tile number -> amplitude index of the tile's element 0: insert_bits with the positions as literals
+    L("__device__ __forceinline__ uint64_t tile_base(uint64_t t) {");
+    L("  uint64_t w = t << kTileLow;");
+    for (uint32_t j = 0; j < ins.npos; ++j) {
+      const std::string p = N(ins.pos[j]);
+      L("  w = ((w >> " + p + ") << " + N(ins.pos[j] + 1) + ") | (w & ((1ull << " + p + ") - 1ull));");
+    }
+    if (ins.ormask) L("  w |= " + U(ins.ormask) + ";");
+    if (p5 != 5u)  // split rows (see tile_block_base): `ins` was opened with 5 standing for p5; the two bits trade places now
+      L("  w = (w & ~(1ull << " + N(p5) + ")) | (((w >> " + N(p5) + ") & 1ull) << 5);");
+    L("  return w;");
+    L("}");
+    if (fold && fold->g) {
+      // the tiles are stored elsewhere, packed for the multi-GPU exchange (TileStorePerm): the positions as literals.  The map
+      // moves index bits, so it distributes over wave base | access bits | lane offset
+      L("__device__ __forceinline__ uint64_t dst_of(uint64_t x) {");
+      L("  uint64_t top = 0;");
+      for (uint32_t t = 0; t < fold->g; ++t) L("  top |= ((x >> " + N(fold->sel[t]) + ") & 1ull) << " + N(fold->Lg + t) + ";");
+      for (uint32_t t = 0; t < fold->g; ++t) {
+        const std::string p = N(fold->sel_desc[t]);
+        L("  x = ((x >> " + N(fold->sel_desc[t] + 1) + ") << " + p + ") | (x & ((1ull << " + p + ") - 1ull));");
+      }
+      L("  return x | top;");
+      L("}");
+    }
+    // `sliced` (r5): the sweep is launched in parts — `ins` has the slice positions opened too, and the kernel's second parameter
+    // is the part's bits at those positions (ORed into every block's base) instead of the unused tile count
+    L(std::string("extern \"C\" __global__ __launch_bounds__(") + bounds + ") void qip_segment(A* __restrict__ st, uint64_t " + (sliced ? "slice_or" : "ntiles") +
+      (params ? ", const T* __restrict__ P" : "") + (fold && fold->g ? ", A* __restrict__ out" : "") + ") {");
+    L("  extern __shared__ __attribute__((aligned(16))) unsigned char " + buf + "_raw[];");
+    L("  A* " + buf + " = reinterpret_cast<A*>(" + buf + "_raw);");
+    L(std::string("  constexpr bool NT = ") + (nt ? "true" : "false") + ";");
+    L("  const uint32_t tid = threadIdx.x, lane = tid & 63u;");
+    L("  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);");
+  }
+  // the pass's table c[]: register index i of a lane's elements holds tile offset c[i] (bit j of i = tile bit bits[j])
+  std::vector<uint32_t> reg_table(const uint32_t* bits, int nbits) {
+    std::vector<uint32_t> c(1u << nbits, 0u);
+    std::string cs = "    const uint32_t c[" + N(c.size()) + "] = {";
+    for (size_t i = 0; i < c.size(); ++i) {
+      for (int j = 0; j < nbits; ++j)
+        if ((i >> j) & 1) c[i] |= 1u << bits[j];
+      cs += N(c[i]) + "u" + (i + 1 < c.size() ? ", " : "};");
+    }
+    L(cs);
+    return c;
+  }
+  // `merge_diag` (option "tile_merge", tile = 2 only: 1e-12 bar): a RUN of >= 3 consecutive diagonal gates — they all commute —
+  // is applied as products.  Every gate contributes a factor (per lane: its lane-bit and outside-the-tile conditions select
+  // between its entry and 1) to the SET of the lane's elements its register-bit conditions pick; factors of one set are
+  // multiplied together first, then each element takes the product of its sets: QFT's 29 controlled phases after an H cost
+  // ~29 + 4 complex products per lane instead of 4 x 29.  The run starts at gs[k] (gate number gi); returns how many gates it
+  // took, 0 when no such run starts there.
+  uint32_t diag_run(const std::vector<SegGate<T>>& gs, size_t k, uint32_t gi, const std::vector<uint32_t>& c) {
+    size_t ke = k;
+    while (ke < gs.size() && gs[ke].g.kind == 1) ++ke;
+    if (ke - k < 3) return 0;
+    std::vector<uint32_t> sets;  // element masks, in order of first appearance: F<k> is the running product of set k
+    L("    {  // gates " + N(gi) + " .. " + N(gi + (ke - k) - 1) + ": one run of diagonal gates");
+    // (each factor joins its product at once: short live ranges.  `ucond`: a block-uniform condition — a control outside the
+    // tile — stays a BRANCH around the product, as in the gate-by-gate form: no work at all where the control reads 0)
+    auto add = [&](uint32_t mask, const std::string& expr, const std::string& ucond) {
+      if (!mask) return;
+      const std::string open = ucond.empty() ? "" : "if (" + ucond + ") { QIP_KEEP_BRANCH(); ", close = ucond.empty() ? "" : " }";
+      for (size_t s = 0; s < sets.size(); ++s)
+        if (sets[s] == mask) {
+          L("      " + open + "F" + N(s) + " = cmul(F" + N(s) + ", " + expr + ");" + close);
+          return;
+        }
+      if (ucond.empty()) L("      A F" + N(sets.size()) + " = " + expr + ";");
+      else L("      A F" + N(sets.size()) + " = {(T)1, (T)0}; " + open + "F" + N(sets.size()) + " = " + expr + ";" + close);
+      sets.push_back(mask);
+    };
+    for (size_t kj = k; kj < ke; ++kj) {
+      const TileGate<T>& d = gs[kj].g;
+      uint32_t ok = 0;  // elements whose register-bit controls are all 1
+      for (size_t i = 0; i < c.size(); ++i)
+        if ((c[i] & d.cm_reg) == d.cm_reg) ok |= 1u << i;
+      const std::string m0 = amp(d.m[0]), m1 = amp(d.m[1]);
+      const bool u0 = d.m[0].x == (T)1 && d.m[0].y == (T)0, u1 = d.m[1].x == (T)1 && d.m[1].y == (T)0;
+      // the conditions every element of the lane shares: controls outside the tile (block-uniform: a branch) and on lane
+      // bits (a select between the entry and 1)
+      const std::string ucond = d.omask ? "(base & " + U(d.omask) + ") == " + U(d.omask) : "";
+      const std::string lcond = d.cm_lane ? "((tb & " + N(d.cm_lane) + "u) == " + N(d.cm_lane) + "u)" : "";
+      auto guarded = [&](const std::string& f) { return lcond.empty() ? f : "tile_sel(" + lcond + ", " + f + ", A{(T)1, (T)0})"; };
+      if (gs[kj].call == SEG_DIAG_REG) {
+        uint32_t half1 = 0;
+        for (size_t i = 0; i < c.size(); ++i)
+          if ((i >> gs[kj].j[0]) & 1) half1 |= 1u << i;
+        if (!u0) add(ok & ~half1, guarded("A" + m0), ucond);
+        if (!u1) add(ok & half1, guarded("A" + m1), ucond);
+      } else {  // the target is a lane bit or lies outside the tile: one factor for every element the controls pick
+        const std::string one = d.b0 == kTileOutside ? "(((base >> " + N(d.tpos_out) + ") & 1ull) != 0)" : "(((tb >> " + N(d.b0) + ") & 1u) != 0)";
+        add(ok, guarded("tile_sel(" + one + ", A" + m1 + ", A" + m0 + ")"), ucond);
+      }
+    }
+    for (size_t i = 0; i < c.size(); ++i)
+      for (size_t si = 0; si < sets.size(); ++si)
+        if ((sets[si] >> i) & 1u) L("      e[" + N(i) + "] = cmul(F" + N(si) + ", e[" + N(i) + "]);");
+    L("    }");
+    return (uint32_t)(ke - k);
+  }
+  void gate_literal(uint32_t gi, const TileGate<T>& g) {
+    L("    {  // gate " + N(gi));
+    const std::string m0 = amp(g.m[0]), m1 = amp(g.m[1]), m2 = amp(g.m[2]), m3 = amp(g.m[3]);
+    L(std::string("      ") + (params ? "const" : "constexpr") + " TileGate<T> g = {" + N(g.kind) + "u, " + N(g.b0) + "u, " + N(g.b1) + "u, " + N(g.cmask) + "u, " +
+      N(g.nz) + "u, " + N(g.tpos_out) + "u, " + U(g.omask) + ", " + N(g.op) + "u, " + N(g.cm_reg) + "u, " + N(g.cm_lane) + "u, 0u, {" + m0 + ", " + m1 + ", " +
+      m2 + ", " + m3 + "}};");
+  }
+  // Diagonal gates: which entries are the unit is known HERE (a unit is always written as a literal, also in the parametrised
+  // form), so the helpers' run-time "unit entries leave the amplitude untouched" tests are resolved by the generator: an entry
+  // that is the unit emits nothing.  Per amplitude the products are those of pass_diag / the interpreter's switch, in the same order.
+  static std::string gate_call(const SegGate<T>& r) {
+    const TileGate<T>& g = r.g;
+    const bool u0 = g.m[0].x == (T)1 && g.m[0].y == (T)0, u1 = g.m[1].x == (T)1 && g.m[1].y == (T)0;
+    const std::string lane_guard = "{ const bool lane_ok = (tb & g.cm_lane) == g.cm_lane; f.x = lane_ok ? f.x : (T)1; f.y = lane_ok ? f.y : (T)0; } ";
+    std::string out;
+    switch (r.call) {
+      case SEG_DIAG_UNIFORM: {
+        const std::string s0 = u0 ? "" : "pass_scale<T, 0, -1>(g.m[0], e, c, g.cm_reg);", s1 = u1 ? "" : "pass_scale<T, 0, -1>(g.m[1], e, c, g.cm_reg);";
+        return "if ((base >> g.tpos_out) & 1ull) { " + s1 + " } else { " + s0 + " }";
+      }
+      case SEG_DIAG_LANE:
+      case SEG_DIAG_LANE_CTL:
+        return std::string("const bool one = ") + (g.b0 == kTileOutside ? "((base >> g.tpos_out) & 1ull) != 0" : "((tb >> g.b0) & 1u) != 0") +
+               "; A f = tile_sel(one, g.m[1], g.m[0]); " + (r.call == SEG_DIAG_LANE_CTL ? lane_guard : "") + "pass_scale<T, 0, -1>(f, e, c, g.cm_reg);";
+      case SEG_DIAG_REG:
+        for (int half = 0; half < 2; ++half)
+          if (!(half == 0 ? u0 : u1))
+            out += "{ A f = g.m[" + N(half) + "]; " + (g.cm_lane ? lane_guard : "") + "pass_scale<T, " + N(r.j[0]) + ", " + N(half) + ">(f, e, c, g.cm_reg); } ";
+        return out;
+      case SEG_DENSE: return "pass_dense<T, " + N(r.j[0]) + ">(g, e, c, g.cm_reg);";
+      case SEG_DENSE_LANE: return "pass_dense_lane<T, " + N(r.j[0]) + ">(g, e, c, g.cm_reg, (tb & g.cm_lane) == g.cm_lane);";
+      case SEG_SWAP: return "pass_swap<T, " + N(r.j[0]) + ", " + N(r.j[1]) + ">(e, c, g.cm_reg, " + kLaneArgs + ");";
+      default: return out;
+    }
+  }
+  void guarded(const TileGate<T>& g, const std::string& call) {
+    if (g.omask) L("      if ((base & g.omask) == g.omask) { " + call + " }");  // an outside control is 0 for this whole tile
+    else L("      { " + call + " }");
+  }
+  void end_gate() {
+    // one gate at a time: left alone hipcc interleaves neighbouring gates up to the register budget of the launch bound and
+    // then spills (16 - 104 bytes of scratch per lane in the configs[1] segments, 104 vs 90 ms for the circuit)
+    L("      __builtin_amdgcn_sched_barrier(0);");
+    L("    }");
+  }
+};
 // The segment as HIP source (see the block comment above).  Mirrors k_tile_passes statement by statement.
 // (Measured in round 3 and NOT adopted: persistent blocks that prefetch the next tile — into registers, or by LDS-DMA into a
 // second tile slot.  The skeleton of a sweep already overlaps its phases through the five resident blocks per CU: with the
@@ -834,62 +1035,13 @@ template <typename T> static std::string fnum(T v) {
 template <typename T>
 static std::string tile_jit_source(const TileSegmentPlan<T>& plan, const Ins& ins, bool nt, int remap = 0, std::vector<T>* params = nullptr,
                                    bool merge_diag = false, const TileStorePerm* fold = nullptr, bool sliced = false) {
-  // `sliced` (r5): the sweep is launched in parts — `ins` has the slice positions opened too, and the kernel's second parameter
-  // is the part's bits at those positions (ORed into every block's base) instead of the unused tile count
-  const char* tname = std::is_same<T, double>::value ? "double" : "float";
-  std::string o;
-  auto L = [&](const std::string& line) { o += line; o += "\n"; };
-  auto U = [](uint64_t v) { return std::to_string(v) + "ull"; };
-  auto comp = [&](T v) -> std::string {
-    if (!params || v == (T)0 || v == (T)1 || v == (T)-1) return fnum<T>(v);  // (a -0 prints as -0.0 and stays one)
-    params->push_back(v);
-    return "P[" + std::to_string(params->size() - 1) + "]";
-  };
-  auto amp = [&](amp_t<T> a) {
-    const std::string re = comp(a.x);  // fixed evaluation order: the parameter numbering is part of the source
-    const std::string im = comp(a.y);
-    return "{" + re + ", " + im + "}";
-  };
+  SegWriter<T> w(params);
+  auto L = [&](const std::string& line) { w.L(line); };
+  const auto N = SegWriter<T>::N, U = SegWriter<T>::U;
   const TilePassDesc& d = plan.pd;
-  L("#include \"qip_kernels.h\"");
-  L("using namespace qipk;");
-  L(std::string("typedef ") + tname + " T;");
-  L("typedef amp_t<T> A;");
-  // tile number -> amplitude index of the tile's element 0: insert_bits with the positions as literals
-  L("__device__ __forceinline__ uint64_t tile_base(uint64_t t) {");
-  L("  uint64_t w = t << kTileLow;");
-  for (uint32_t j = 0; j < ins.npos; ++j) {
-    const std::string p = std::to_string(ins.pos[j]);
-    L("  w = ((w >> " + p + ") << " + std::to_string(ins.pos[j] + 1) + ") | (w & ((1ull << " + p + ") - 1ull));");
-  }
-  if (ins.ormask) L("  w |= " + U(ins.ormask) + ";");
-  if (d.p5 != 5u)  // split rows (see tile_block_base): `ins` was opened with 5 standing for p5; the two bits trade places now
-    L("  w = (w & ~(1ull << " + std::to_string(d.p5) + ")) | (((w >> " + std::to_string(d.p5) + ") & 1ull) << 5);");
-  L("  return w;");
-  L("}");
-  if (fold && fold->g) {
-    // the tiles are stored elsewhere, packed for the multi-GPU exchange (TileStorePerm): the positions as literals
-    L("__device__ __forceinline__ uint64_t dst_of(uint64_t x) {");
-    L("  uint64_t top = 0;");
-    for (uint32_t t = 0; t < fold->g; ++t)
-      L("  top |= ((x >> " + std::to_string(fold->sel[t]) + ") & 1ull) << " + std::to_string(fold->Lg + t) + ";");
-    for (uint32_t t = 0; t < fold->g; ++t) {
-      const std::string p = std::to_string(fold->sel_desc[t]);
-      L("  x = ((x >> " + std::to_string(fold->sel_desc[t] + 1) + ") << " + p + ") | (x & ((1ull << " + p + ") - 1ull));");
-    }
-    L("  return x | top;");
-    L("}");
-  }
-  L(std::string("extern \"C\" __global__ __launch_bounds__(kTileBlock, 5) void qip_segment(A* __restrict__ st, uint64_t ") + (sliced ? "slice_or" : "ntiles") +
-    (params ? ", const T* __restrict__ P" : "") + (fold && fold->g ? ", A* __restrict__ out" : "") + ") {");
-  L("  extern __shared__ __attribute__((aligned(16))) unsigned char tile_raw[];");
-  L("  A* tile = reinterpret_cast<A*>(tile_raw);");
-  L(std::string("  constexpr bool NT = ") + (nt ? "true" : "false") + ";");
-  L("  const uint32_t tid = threadIdx.x, lane = tid & 63u;");
-  L("  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);");
+  w.prologue(ins, d.p5, fold, "kTileBlock, 5", sliced, "tile", nt);
   L("  uint64_t wave_off = 0;");
-  for (int j = 0; j < kTileWaveBits; ++j)
-    L("  wave_off |= (uint64_t)((wave >> " + std::to_string(j) + ") & 1u) << " + std::to_string(d.hpos[j]) + ";");
+  for (int j = 0; j < kTileWaveBits; ++j) L("  wave_off |= (uint64_t)((wave >> " + N(j) + ") & 1u) << " + N(d.hpos[j]) + ";");
   L("  const uint32_t slot_tid = tile_slot<A>(tid);");
   auto ub = [&](int u) {
     uint64_t off = 0;
@@ -915,191 +1067,74 @@ static std::string tile_jit_source(const TileSegmentPlan<T>& plan, const Ins& in
     L("  blk = ((blk >> 3) & ((1ull << " + J + ") - 1ull)) | ((blk & 7ull) << " + J + ") | (((blk >> 3) >> " + J + ") << (" + J + " + 3));");
   }
   L(std::string("  const uint64_t base = tile_base(blk)") + (sliced ? " | slice_or" : "") + ", wbase = base | wave_off;");
-  L("  const uint32_t lane_off = tile_lane_off(lane, " + std::to_string(d.p5) + "u);");
-  for (int u = 0; u < 8; ++u) L("  x[" + std::to_string(u) + "] = ldg<NT>(st + (wbase | " + ub(u) + ") + lane_off);");
+  L("  const uint32_t lane_off = tile_lane_off(lane, " + N(d.p5) + "u);");
+  for (int u = 0; u < 8; ++u) L("  x[" + N(u) + "] = ldg<NT>(st + (wbase | " + ub(u) + ") + lane_off);");
   L("  const uint32_t tidv = tid;");
-  for (int u = 0; u < 8; ++u)
-    L("    tile[slot_tid ^ tile_slot<A>(" + std::to_string(u) + "u << kTileLaneBits)] = x[" + std::to_string(u) + "];");
+  for (int u = 0; u < 8; ++u) L("    tile[slot_tid ^ tile_slot<A>(" + N(u) + "u << kTileLaneBits)] = x[" + N(u) + "];");
   L("  __syncthreads();");
   for (uint32_t pi = 0; pi < d.npasses; ++pi) {
     const TilePass& ps = d.pass[pi];
-    L("  {  // pass " + std::to_string(pi));
+    L("  {  // pass " + N(pi));
     // the pass's LDS addresses depend on the lane id alone: left alone hipcc computes those of EVERY pass up front and keeps
     // them live (spills in segments of many passes); an opaque copy of the id per pass pins them behind the barrier before it
     L("    uint32_t tidp = tidv;");
     L("    asm volatile(\"\" : \"+v\"(tidp));");
     L("    uint32_t tb = 0;");
-    for (int k = 0; k < kTileLaneBits; ++k)
-      L("    tb |= ((tidp >> " + std::to_string(k) + ") & 1u) << " + std::to_string((unsigned)((ps.lanepos >> (4 * k)) & 15ull)) + ";");
+    for (int k = 0; k < kTileLaneBits; ++k) L("    tb |= ((tidp >> " + N(k) + ") & 1u) << " + N((ps.lanepos >> (4 * k)) & 15ull) + ";");
     L("    const uint32_t slot_tb = tile_slot<A>(tb);");
-    std::string cs = "    const uint32_t c[8] = {";
-    for (int i = 0; i < 8; ++i) {
-      const uint32_t c = ((uint32_t)(i & 1) << ps.pb[0]) | ((uint32_t)((i >> 1) & 1) << ps.pb[1]) | ((uint32_t)((i >> 2) & 1) << ps.pb[2]);
-      cs += std::to_string(c) + "u" + (i < 7 ? ", " : "};");
-    }
-    L(cs);
+    const std::vector<uint32_t> c = w.reg_table(ps.pb, 3);
     L("    A e[8];");
-    for (int i = 0; i < 8; ++i) L("    e[" + std::to_string(i) + "] = tile[slot_tb ^ tile_slot<A>(c[" + std::to_string(i) + "])];");
+    for (int i = 0; i < 8; ++i) L("    e[" + N(i) + "] = tile[slot_tb ^ tile_slot<A>(c[" + N(i) + "])];");
+    // the gates as the pass resolved them (TOP_*): the host already knows which bits are register bits
+    std::vector<SegGate<T>> gs;
     for (uint32_t gi = ps.first; gi < ps.first + ps.count; ++gi) {
       const TileGate<T>& g = plan.gates[gi];
-      // `merge_diag` (option "tile_merge", tile = 2 only: 1e-12 bar): a RUN of consecutive diagonal gates — they all commute —
-      // is applied as products.  Every gate contributes a factor (per lane: its lane-bit and outside-the-tile conditions
-      // select between its entry and 1) to the SET of the lane's eight elements its register-bit conditions pick; factors of
-      // one set are multiplied together first, then each element takes the product of its sets: QFT's 29 controlled phases
-      // after an H cost ~29 + 4 complex products per lane instead of 4 x 29.
-      if (merge_diag && g.kind == 1) {
-        uint32_t ge = gi;
-        while (ge < ps.first + ps.count && plan.gates[ge].kind == 1) ++ge;
-        if (ge - gi >= 3) {
-          std::vector<uint32_t> sets;  // element masks, in order of first appearance: F<k> is the running product of set k
-          L("    {  // gates " + std::to_string(gi) + " .. " + std::to_string(ge - 1) + ": one run of diagonal gates");
-          // (each factor joins its product at once: short live ranges.  `ucond`: a block-uniform condition — a control outside the
-          // tile — stays a BRANCH around the product, as in the gate-by-gate form: no work at all where the control reads 0)
-          auto add = [&](uint32_t mask, const std::string& expr, const std::string& ucond) {
-            if (!mask) return;
-            const std::string open = ucond.empty() ? "" : "if (" + ucond + ") { QIP_KEEP_BRANCH(); ", close = ucond.empty() ? "" : " }";
-            for (size_t k = 0; k < sets.size(); ++k)
-              if (sets[k] == mask) {
-                L("      " + open + "F" + std::to_string(k) + " = cmul(F" + std::to_string(k) + ", " + expr + ");" + close);
-                return;
-              }
-            if (ucond.empty()) L("      A F" + std::to_string(sets.size()) + " = " + expr + ";");
-            else L("      A F" + std::to_string(sets.size()) + " = {(T)1, (T)0}; " + open + "F" + std::to_string(sets.size()) + " = " + expr + ";" + close);
-            sets.push_back(mask);
-          };
-          for (uint32_t gj = gi; gj < ge; ++gj) {
-            const TileGate<T>& d = plan.gates[gj];
-            uint32_t ok = 0;  // elements whose register-bit controls are all 1
-            for (int i = 0; i < 8; ++i) {
-              const uint32_t ci = ((uint32_t)(i & 1) << ps.pb[0]) | ((uint32_t)((i >> 1) & 1) << ps.pb[1]) | ((uint32_t)((i >> 2) & 1) << ps.pb[2]);
-              if ((ci & d.cm_reg) == d.cm_reg) ok |= 1u << i;
-            }
-            const std::string m0 = amp(d.m[0]), m1 = amp(d.m[1]);
-            const bool u0 = d.m[0].x == (T)1 && d.m[0].y == (T)0, u1 = d.m[1].x == (T)1 && d.m[1].y == (T)0;
-            // the conditions every element of the lane shares: controls outside the tile (block-uniform: a branch) and on lane
-            // bits (a select between the entry and 1)
-            const std::string ucond = d.omask ? "(base & " + U(d.omask) + ") == " + U(d.omask) : "";
-            const std::string lcond = d.cm_lane ? "((tb & " + std::to_string(d.cm_lane) + "u) == " + std::to_string(d.cm_lane) + "u)" : "";
-            auto guarded = [&](const std::string& f) { return lcond.empty() ? f : "tile_sel(" + lcond + ", " + f + ", A{(T)1, (T)0})"; };
-            if (d.op >= TOP_DIAG_REG0 && d.op <= TOP_DIAG_REG2) {
-              const int J = (int)(d.op - TOP_DIAG_REG0);
-              uint32_t half1 = 0;
-              for (int i = 0; i < 8; ++i)
-                if ((i >> J) & 1) half1 |= 1u << i;
-              if (!u0) add(ok & ~half1, guarded("A" + m0), ucond);
-              if (!u1) add(ok & half1, guarded("A" + m1), ucond);
-            } else {  // the target is a lane bit or lies outside the tile: one factor for every element the controls pick
-              const std::string one = d.b0 == kTileOutside ? "(((base >> " + std::to_string(d.tpos_out) + ") & 1ull) != 0)"
-                                                           : "(((tb >> " + std::to_string(d.b0) + ") & 1u) != 0)";
-              add(ok, guarded("tile_sel(" + one + ", A" + m1 + ", A" + m0 + ")"), ucond);
-            }
-          }
-          for (int i = 0; i < 8; ++i)
-            for (size_t si = 0; si < sets.size(); ++si)
-              if ((sets[si] >> i) & 1u) L("      e[" + std::to_string(i) + "] = cmul(F" + std::to_string(si) + ", e[" + std::to_string(i) + "]);");
-          L("    }");
-          gi = ge - 1;
+      const uint32_t op = g.op;
+      static const int sa[3] = {0, 0, 1}, sb[3] = {1, 2, 2};  // TOP_SWAP_01, _02, _12
+      SegGate<T> r = {g};
+      if (op == TOP_DIAG_UNIFORM) r.call = SEG_DIAG_UNIFORM;
+      else if (op == TOP_DIAG_LANE) r.call = SEG_DIAG_LANE;
+      else if (op == TOP_DIAG_LANE_CTL) r.call = SEG_DIAG_LANE_CTL;
+      else if (op >= TOP_DIAG_REG0 && op <= TOP_DIAG_REG2) r = {g, SEG_DIAG_REG, {(int)(op - TOP_DIAG_REG0)}};
+      else if (op >= TOP_DENSE0 && op <= TOP_DENSE2) r = {g, SEG_DENSE, {(int)(op - TOP_DENSE0)}};
+      else if (op >= TOP_DENSE_LANE0 && op <= TOP_DENSE_LANE2) r = {g, SEG_DENSE_LANE, {(int)(op - TOP_DENSE_LANE0)}};
+      else if (op >= TOP_SWAP_01 && op <= TOP_SWAP_12) r = {g, SEG_SWAP, {sa[op - TOP_SWAP_01], sb[op - TOP_SWAP_01]}};
+      gs.push_back(r);
+    }
+    for (size_t k = 0; k < gs.size(); ++k) {
+      const uint32_t gi = ps.first + (uint32_t)k;
+      if (merge_diag)
+        if (const uint32_t run = w.diag_run(gs, k, gi, c)) {
+          k += run - 1;
           continue;
         }
+      const TileGate<T>& g = gs[k].g;
+      w.gate_literal(gi, g);
+      std::string call = SegWriter<T>::gate_call(gs[k]);
+      static const int ja[6] = {0, 0, 1, 1, 2, 2}, jb[6] = {1, 2, 0, 2, 0, 1};
+      if (g.op >= TOP_DENSE2Q_01 && g.op <= TOP_DENSE2Q_21) {
+        // (the 4x4 matrix as components, also when parametrised: unlike the wide tile's block)
+        const uint32_t v = g.op - TOP_DENSE2Q_01;
+        call = w.matrix_literal(&plan.mats[16 * g.nz], 16) + "pass_dense2<T, " + N(ja[v]) + ", " + N(jb[v]) + ">(M, e, c, g.cm_reg, " + SegWriter<T>::kLaneArgs + ");";
+      } else if (g.op >= TOP_DENSE3Q_012 && g.op <= TOP_DENSE3Q_210) {
+        const uint32_t v = g.op - TOP_DENSE3Q_012;
+        call = w.matrix(&plan.mats[16 * g.nz], 64) + "pass_dense3<T, " + N(ja[v]) + ", " + N(jb[v]) + ", " + N(3 - ja[v] - jb[v]) + ">(M, e, " +
+               SegWriter<T>::kLaneArgs + ");";
       }
-      L("    {  // gate " + std::to_string(gi));
-      {
-        const std::string m0 = amp(g.m[0]), m1 = amp(g.m[1]), m2 = amp(g.m[2]), m3 = amp(g.m[3]);
-        L(std::string("      ") + (params ? "const" : "constexpr") + " TileGate<T> g = {" + std::to_string(g.kind) + "u, " + std::to_string(g.b0) + "u, " +
-          std::to_string(g.b1) + "u, " + std::to_string(g.cmask) + "u, " + std::to_string(g.nz) + "u, " + std::to_string(g.tpos_out) + "u, " + U(g.omask) +
-          ", " + std::to_string(g.op) + "u, " + std::to_string(g.cm_reg) + "u, " + std::to_string(g.cm_lane) + "u, 0u, {" + m0 + ", " + m1 + ", " + m2 +
-          ", " + m3 + "}};");
-      }
-      const std::string lane_args = "g.cm_lane != 0u, (tb & g.cm_lane) == g.cm_lane";
-      std::string call;
-      switch (g.op) {
-        // Diagonal gates: which entries are the unit is known HERE (a unit is always written as a literal, also in the
-        // parametrised form), so the helpers' run-time "unit entries leave the amplitude untouched" tests are resolved by
-        // the generator: an entry that is the unit emits nothing.  Per amplitude the products are those of pass_diag / the
-        // interpreter's switch, in the same order.
-        case TOP_DIAG_UNIFORM: {
-          const bool u0 = g.m[0].x == (T)1 && g.m[0].y == (T)0, u1 = g.m[1].x == (T)1 && g.m[1].y == (T)0;
-          const std::string s0 = u0 ? "" : "pass_scale<T, 0, -1>(g.m[0], e, c, g.cm_reg);", s1 = u1 ? "" : "pass_scale<T, 0, -1>(g.m[1], e, c, g.cm_reg);";
-          call = "if ((base >> g.tpos_out) & 1ull) { " + s1 + " } else { " + s0 + " }";
-          break;
-        }
-        case TOP_DIAG_LANE:
-        case TOP_DIAG_LANE_CTL:
-          call = std::string("const bool one = ") + (g.b0 == kTileOutside ? "((base >> g.tpos_out) & 1ull) != 0" : "((tb >> g.b0) & 1u) != 0") +
-                 "; A f = tile_sel(one, g.m[1], g.m[0]); " +
-                 (g.op == TOP_DIAG_LANE_CTL ? "{ const bool lane_ok = (tb & g.cm_lane) == g.cm_lane; f.x = lane_ok ? f.x : (T)1; f.y = lane_ok ? f.y : (T)0; } " : "") +
-                 "pass_scale<T, 0, -1>(f, e, c, g.cm_reg);";
-          break;
-        case TOP_DIAG_REG0: case TOP_DIAG_REG1: case TOP_DIAG_REG2: {
-          const std::string J = std::to_string(g.op - TOP_DIAG_REG0);
-          call.clear();
-          for (int half = 0; half < 2; ++half) {
-            if (g.m[half].x == (T)1 && g.m[half].y == (T)0) continue;
-            const std::string hs = std::to_string(half);
-            call += "{ A f = g.m[" + hs + "]; ";
-            if (g.cm_lane) call += "{ const bool lane_ok = (tb & g.cm_lane) == g.cm_lane; f.x = lane_ok ? f.x : (T)1; f.y = lane_ok ? f.y : (T)0; } ";
-            call += "pass_scale<T, " + J + ", " + hs + ">(f, e, c, g.cm_reg); } ";
-          }
-          break;
-        }
-        case TOP_DENSE0: case TOP_DENSE1: case TOP_DENSE2:
-          call = "pass_dense<T, " + std::to_string(g.op - TOP_DENSE0) + ">(g, e, c, g.cm_reg);";
-          break;
-        case TOP_DENSE_LANE0: case TOP_DENSE_LANE1: case TOP_DENSE_LANE2:
-          call = "pass_dense_lane<T, " + std::to_string(g.op - TOP_DENSE_LANE0) + ">(g, e, c, g.cm_reg, (tb & g.cm_lane) == g.cm_lane);";
-          break;
-        case TOP_DENSE2Q_01: case TOP_DENSE2Q_02: case TOP_DENSE2Q_10: case TOP_DENSE2Q_12: case TOP_DENSE2Q_20: case TOP_DENSE2Q_21: {
-          static const int ja[6] = {0, 0, 1, 1, 2, 2}, jb[6] = {1, 2, 0, 2, 0, 1};
-          std::string m = "const A M[16] = {";
-          for (int e = 0; e < 16; ++e) m += amp(plan.mats[16 * g.nz + e]) + (e < 15 ? ", " : "}; ");
-          call = m + "pass_dense2<T, " + std::to_string(ja[g.op - TOP_DENSE2Q_01]) + ", " + std::to_string(jb[g.op - TOP_DENSE2Q_01]) + ">(M, e, c, g.cm_reg, " + lane_args + ");";
-          break;
-        }
-        case TOP_DENSE3Q_012: case TOP_DENSE3Q_021: case TOP_DENSE3Q_102: case TOP_DENSE3Q_120: case TOP_DENSE3Q_201: case TOP_DENSE3Q_210: {
-          static const int ja[6] = {0, 0, 1, 1, 2, 2}, jb[6] = {1, 2, 0, 2, 0, 1};
-          const int a = ja[g.op - TOP_DENSE3Q_012], b = jb[g.op - TOP_DENSE3Q_012];
-          const std::string tail = "pass_dense3<T, " + std::to_string(a) + ", " + std::to_string(b) + ", " + std::to_string(3 - a - b) + ">(M, e, " + lane_args + ");";
-          if (params) {
-            // r4: the 8 x 8 matrix as ONE contiguous block of the parameter array, read row by row through a pointer like the
-            // interpreter does (wave-uniform scalar loads as they are needed).  Spelt out as 64 named components, all 128
-            // scalars were live at once: the dense-k3 Grover segments ran SLOWER compiled than interpreted (108.9 vs 101.4 ms).
-            if (params->size() & 1) params->push_back((T)0);  // (16-byte alignment of the block for Complex<f64>)
-            const size_t off = params->size();
-            for (int e = 0; e < 64; ++e) {
-              params->push_back(plan.mats[16 * g.nz + e].x);
-              params->push_back(plan.mats[16 * g.nz + e].y);
-            }
-            call = "const A* __restrict__ M = reinterpret_cast<const A*>(P + " + std::to_string(off) + "); " + tail;
-          } else {
-            std::string m = "const A M[64] = {";
-            for (int e = 0; e < 64; ++e) m += amp(plan.mats[16 * g.nz + e]) + (e < 63 ? ", " : "}; ");
-            call = m + tail;
-          }
-          break;
-        }
-        case TOP_SWAP_01: call = "pass_swap<T, 0, 1>(e, c, g.cm_reg, " + lane_args + ");"; break;
-        case TOP_SWAP_02: call = "pass_swap<T, 0, 2>(e, c, g.cm_reg, " + lane_args + ");"; break;
-        case TOP_SWAP_12: call = "pass_swap<T, 1, 2>(e, c, g.cm_reg, " + lane_args + ");"; break;
-        default: break;
-      }
-      if (g.omask) L("      if ((base & g.omask) == g.omask) { " + call + " }");  // an outside control is 0 for this whole tile
-      else L("      { " + call + " }");
-      // one gate at a time: left alone hipcc interleaves neighbouring gates up to the register budget of the launch bound and
-      // then spills (16 - 104 bytes of scratch per lane in the configs[1] segments, 104 vs 90 ms for the circuit)
-      L("      __builtin_amdgcn_sched_barrier(0);");
-      L("    }");
+      w.guarded(g, call);
+      w.end_gate();
     }
-    for (int i = 0; i < 8; ++i) L("    tile[slot_tb ^ tile_slot<A>(c[" + std::to_string(i) + "])] = e[" + std::to_string(i) + "];");
+    for (int i = 0; i < 8; ++i) L("    tile[slot_tb ^ tile_slot<A>(c[" + N(i) + "])] = e[" + N(i) + "];");
     L("    __syncthreads();");
     L("  }");
   }
   for (int u = 0; u < 8; ++u)
     if (fold && fold->g)
-      L("  stg<NT>(out + dst_of(wbase | " + ub(u) + ") + dst_of(lane_off), tile[slot_tid ^ tile_slot<A>(" + std::to_string(u) + "u << kTileLaneBits)]);");
+      L("  stg<NT>(out + dst_of(wbase | " + ub(u) + ") + dst_of(lane_off), tile[slot_tid ^ tile_slot<A>(" + N(u) + "u << kTileLaneBits)]);");
     else
-      L("  stg<NT>(st + (wbase | " + ub(u) + ") + lane_off, tile[slot_tid ^ tile_slot<A>(" + std::to_string(u) + "u << kTileLaneBits)]);");
+      L("  stg<NT>(st + (wbase | " + ub(u) + ") + lane_off, tile[slot_tid ^ tile_slot<A>(" + N(u) + "u << kTileLaneBits)]);");
   L("}");
-  return o;
+  return w.o;
 }
 
 // ---- wide tiles (r4, option "tile_wide"): the segment's source for the register-resident 13-bit tile ------------------------------
@@ -1121,56 +1156,12 @@ int64_t g_tile_wide_dense3_inline = 1;  // r5: run on MI355X — bit-identical t
 template <typename T>
 static std::string wide_jit_source(const WidePlan<T>& plan, const Ins& ins, bool nt, std::vector<T>* params, bool merge_diag = false, bool pin = false,
                                    bool dense3_inline = false, bool sliced = false, const TileStorePerm* fold = nullptr) {
-  const char* tname = std::is_same<T, double>::value ? "double" : "float";
   constexpr uint32_t SW = sizeof(amp_t<T>) == 16 ? 4u : 5u;  // tile_slot's fold width
   auto slot = [&](uint32_t t) { return t ^ ((t >> SW) & ((1u << SW) - 1u)); };
-  std::string o;
-  auto L = [&](const std::string& line) { o += line; o += "\n"; };
-  auto U = [](uint64_t v) { return std::to_string(v) + "ull"; };
-  auto N = [](uint64_t v) { return std::to_string(v); };
-  auto comp = [&](T v) -> std::string {
-    if (!params || v == (T)0 || v == (T)1 || v == (T)-1) return fnum<T>(v);
-    params->push_back(v);
-    return "P[" + std::to_string(params->size() - 1) + "]";
-  };
-  auto amp = [&](amp_t<T> a) {
-    const std::string re = comp(a.x);
-    const std::string im = comp(a.y);
-    return "{" + re + ", " + im + "}";
-  };
-  L("#include \"qip_kernels.h\"");
-  L("using namespace qipk;");
-  L(std::string("typedef ") + tname + " T;");
-  L("typedef amp_t<T> A;");
-  L("__device__ __forceinline__ uint64_t tile_base(uint64_t t) {");
-  L("  uint64_t w = t << kTileLow;");
-  for (uint32_t j = 0; j < ins.npos; ++j) {
-    const std::string p = N(ins.pos[j]);
-    L("  w = ((w >> " + p + ") << " + N(ins.pos[j] + 1) + ") | (w & ((1ull << " + p + ") - 1ull));");
-  }
-  if (plan.p5 != 5u) L("  w = (w & ~(1ull << " + N(plan.p5) + ")) | (((w >> " + N(plan.p5) + ") & 1ull) << 5);");
-  L("  return w;");
-  L("}");
-  if (fold && fold->g) {
-    // r5: the tiles are stored elsewhere, packed for the multi-GPU exchange (TileStorePerm), exactly as the 11-bit sweeps do it: the
-    // map moves index bits, so it distributes over wave base | access bits | lane offset
-    L("__device__ __forceinline__ uint64_t dst_of(uint64_t x) {");
-    L("  uint64_t top = 0;");
-    for (uint32_t t = 0; t < fold->g; ++t) L("  top |= ((x >> " + N(fold->sel[t]) + ") & 1ull) << " + N(fold->Lg + t) + ";");
-    for (uint32_t t = 0; t < fold->g; ++t) {
-      const std::string p = N(fold->sel_desc[t]);
-      L("  x = ((x >> " + N(fold->sel_desc[t] + 1) + ") << " + p + ") | (x & ((1ull << " + p + ") - 1ull));");
-    }
-    L("  return x | top;");
-    L("}");
-  }
-  L(std::string("extern \"C\" __global__ __launch_bounds__(256, 2) void qip_segment(A* __restrict__ st, uint64_t ") + (sliced ? "slice_or" : "ntiles") +
-    (params ? ", const T* __restrict__ P" : "") + (fold && fold->g ? ", A* __restrict__ out" : "") + ") {");
-  L("  extern __shared__ __attribute__((aligned(16))) unsigned char buf_raw[];");
-  L("  A* buf = reinterpret_cast<A*>(buf_raw);");
-  L(std::string("  constexpr bool NT = ") + (nt ? "true" : "false") + ";");
-  L("  const uint32_t tid = threadIdx.x, lane = tid & 63u;");
-  L("  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);");
+  SegWriter<T> w(params);
+  auto L = [&](const std::string& line) { w.L(line); };
+  const auto N = SegWriter<T>::N, U = SegWriter<T>::U;
+  w.prologue(ins, plan.p5, fold, "256, 2", sliced, "buf", nt);
   if (!sliced) L("  (void)ntiles;");
   L(std::string("  const uint64_t base = tile_base(blockIdx.x + (uint64_t)blockIdx.y * gridDim.x)") + (sliced ? " | slice_or;" : ";"));
   L("  const uint64_t wbase = base | ((uint64_t)(wave & 1u) << " + N(plan.high[0]) + ") | ((uint64_t)(wave >> 1) << " + N(plan.high[1]) + ");");
@@ -1205,11 +1196,11 @@ static std::string wide_jit_source(const WidePlan<T>& plan, const Ins& ins, bool
         L("    rb |= ((tidp >> " + N(k) + ") & 1u) << " + N(ps.bufpos[ps.L[k]]) + ";");
       }
       L("    const uint32_t swa = tile_slot<A>(wa), srb = tile_slot<A>(rb);");
-      auto split = [&](const WidePass& w, int (&jq)[2], int (&jo)[3]) {
+      auto split = [&](const WidePass& wp, int (&jq)[2], int (&jo)[3]) {
         int no = 0;
         for (int j = 0; j < kWideRegBits; ++j) {
-          if (w.R[j] == ps.q[0]) jq[0] = j;
-          else if (w.R[j] == ps.q[1]) jq[1] = j;
+          if (wp.R[j] == ps.q[0]) jq[0] = j;
+          else if (wp.R[j] == ps.q[1]) jq[1] = j;
           else jo[no++] = j;
         }
       };
@@ -1261,135 +1252,46 @@ static std::string wide_jit_source(const WidePlan<T>& plan, const Ins& ins, bool
     for (int k = 0; k < 8; ++k) L("    tb |= ((tidq >> " + N(k) + ") & 1u) << " + N(ps.L[k]) + ";");
     uint32_t rmask = 0;
     for (int j = 0; j < kWideRegBits; ++j) rmask |= 1u << ps.R[j];
-    std::string cs = "    const uint32_t c[32] = {";
-    for (int i = 0; i < 32; ++i) {
-      uint32_t c = 0;
-      for (int j = 0; j < kWideRegBits; ++j)
-        if ((i >> j) & 1) c |= 1u << ps.R[j];
-      cs += N(c) + "u" + (i < 31 ? ", " : "};");
-    }
-    L(cs);
+    const std::vector<uint32_t> c = w.reg_table(ps.R, kWideRegBits);
     L("    A (&e)[32] = " + e + ";");
+    // the gates resolved against this arrangement: controls split into register and lane bits, targets looked up as register
+    // bits (op stays 0: no interpreter reads it)
+    std::vector<SegGate<T>> gs;
     for (uint32_t gi = ps.first; gi < ps.first + ps.count; ++gi) {
       TileGate<T> g = plan.gates[gi];
       g.cm_reg = g.cmask & rmask;
       g.cm_lane = g.cmask & ~rmask;
       g.op = 0;
-      // `merge_diag` (option "tile_merge", tile = 2 only: 1e-12 bar): a run of consecutive diagonal gates as products — every
-      // gate contributes a factor to the SET of the lane's 32 elements its register-bit conditions pick, the factors of one set
-      // are multiplied together as they come, each element then takes the product of its sets (the 11-bit generator's scheme
-      // over 32 elements: QFT's runs of controlled phases)
-      if (merge_diag && g.kind == 1) {
-        uint32_t ge = gi;
-        while (ge < ps.first + ps.count && plan.gates[ge].kind == 1) ++ge;
-        if (ge - gi >= 3) {
-          std::vector<uint32_t> sets;
-          L("    {  // gates " + N(gi) + " .. " + N(ge - 1) + ": one run of diagonal gates");
-          auto add = [&](uint32_t mask, const std::string& expr, const std::string& ucond) {
-            if (!mask) return;
-            const std::string open = ucond.empty() ? "" : "if (" + ucond + ") { QIP_KEEP_BRANCH(); ", close = ucond.empty() ? "" : " }";
-            for (size_t k = 0; k < sets.size(); ++k)
-              if (sets[k] == mask) {
-                L("      " + open + "F" + N(k) + " = cmul(F" + N(k) + ", " + expr + ");" + close);
-                return;
-              }
-            if (ucond.empty()) L("      A F" + N(sets.size()) + " = " + expr + ";");
-            else L("      A F" + N(sets.size()) + " = {(T)1, (T)0}; " + open + "F" + N(sets.size()) + " = " + expr + ";" + close);
-            sets.push_back(mask);
-          };
-          for (uint32_t gj = gi; gj < ge; ++gj) {
-            const TileGate<T>& d = plan.gates[gj];
-            const uint32_t d_reg = d.cmask & rmask, d_lane = d.cmask & ~rmask;
-            uint32_t ok = 0;  // elements whose register-bit controls are all 1
-            for (int i = 0; i < 32; ++i) {
-              uint32_t ci = 0;
-              for (int j = 0; j < kWideRegBits; ++j)
-                if ((i >> j) & 1) ci |= 1u << ps.R[j];
-              if ((ci & d_reg) == d_reg) ok |= 1u << i;
-            }
-            const std::string m0 = amp(d.m[0]), m1 = amp(d.m[1]);
-            const bool u0 = d.m[0].x == (T)1 && d.m[0].y == (T)0, u1 = d.m[1].x == (T)1 && d.m[1].y == (T)0;
-            const std::string ucond = d.omask ? "(base & " + U(d.omask) + ") == " + U(d.omask) : "";
-            const std::string lcond = d_lane ? "((tb & " + N(d_lane) + "u) == " + N(d_lane) + "u)" : "";
-            auto guarded = [&](const std::string& f) { return lcond.empty() ? f : "tile_sel(" + lcond + ", " + f + ", A{(T)1, (T)0})"; };
-            const int J = d.b0 == kTileOutside ? -1 : jof(d.b0);
-            if (J >= 0) {
-              uint32_t half1 = 0;
-              for (int i = 0; i < 32; ++i)
-                if ((i >> J) & 1) half1 |= 1u << i;
-              if (!u0) add(ok & ~half1, guarded("A" + m0), ucond);
-              if (!u1) add(ok & half1, guarded("A" + m1), ucond);
-            } else {
-              const std::string one = d.b0 == kTileOutside ? "(((base >> " + N(d.tpos_out) + ") & 1ull) != 0)" : "(((tb >> " + N(d.b0) + ") & 1u) != 0)";
-              add(ok, guarded("tile_sel(" + one + ", A" + m1 + ", A" + m0 + ")"), ucond);
-            }
-          }
-          for (int i = 0; i < 32; ++i)
-            for (size_t si = 0; si < sets.size(); ++si)
-              if ((sets[si] >> i) & 1u) L("      e[" + N(i) + "] = cmul(F" + N(si) + ", e[" + N(i) + "]);");
-          L("    }");
-          gi = ge - 1;
+      const int J = g.b0 == kTileOutside ? -1 : jof(g.b0);
+      SegGate<T> r = {g};
+      if (g.kind == 1 && J >= 0) r = {g, SEG_DIAG_REG, {J}};
+      else if (g.kind == 1) r.call = g.b0 == kTileOutside && !g.cm_lane ? SEG_DIAG_UNIFORM : g.cm_lane ? SEG_DIAG_LANE_CTL : SEG_DIAG_LANE;
+      else if (g.kind == 0) r = {g, g.cm_lane ? SEG_DENSE_LANE : SEG_DENSE, {jof(g.b0)}};
+      else if (g.kind == 2) r = {g, SEG_SWAP, {jof(g.b0), jof(g.b1)}};
+      gs.push_back(r);
+    }
+    for (size_t k = 0; k < gs.size(); ++k) {
+      const uint32_t gi = ps.first + (uint32_t)k;
+      if (merge_diag)
+        if (const uint32_t run = w.diag_run(gs, k, gi, c)) {
+          k += run - 1;
           continue;
         }
-      }
-      L("    {  // gate " + N(gi));
-      {
-        const std::string m0 = amp(g.m[0]), m1 = amp(g.m[1]), m2 = amp(g.m[2]), m3 = amp(g.m[3]);
-        L(std::string("      ") + (params ? "const" : "constexpr") + " TileGate<T> g = {" + N(g.kind) + "u, " + N(g.b0) + "u, " + N(g.b1) + "u, " + N(g.cmask) + "u, " +
-          N(g.nz) + "u, " + N(g.tpos_out) + "u, " + U(g.omask) + ", 0u, " + N(g.cm_reg) + "u, " + N(g.cm_lane) + "u, 0u, {" + m0 + ", " + m1 + ", " + m2 + ", " + m3 + "}};");
-      }
-      const std::string lane_args = "g.cm_lane != 0u, (tb & g.cm_lane) == g.cm_lane";
-      auto matrix = [&](int cnt) {  // the gate's 4x4 / 8x8 matrix: a block of the parameter array, or literals
-        if (params) {
-          if (params->size() & 1) params->push_back((T)0);
-          const size_t off = params->size();
-          for (int k = 0; k < cnt; ++k) {
-            params->push_back(plan.mats[16 * g.nz + k].x);
-            params->push_back(plan.mats[16 * g.nz + k].y);
-          }
-          return "const A* __restrict__ M = reinterpret_cast<const A*>(P + " + N(off) + "); ";
-        }
-        std::string m = "const A M[" + N(cnt) + "] = {";
-        for (int k = 0; k < cnt; ++k) m += amp(plan.mats[16 * g.nz + k]) + (k + 1 < cnt ? ", " : "}; ");
-        return m;
-      };
-      std::string call;
-      if (g.kind == 1) {
-        const bool u0 = g.m[0].x == (T)1 && g.m[0].y == (T)0, u1 = g.m[1].x == (T)1 && g.m[1].y == (T)0;
-        const int J = g.b0 == kTileOutside ? -1 : jof(g.b0);
-        const std::string guard = g.cm_lane ? "{ const bool lane_ok = (tb & g.cm_lane) == g.cm_lane; f.x = lane_ok ? f.x : (T)1; f.y = lane_ok ? f.y : (T)0; } " : "";
-        if (J >= 0) {
-          for (int half = 0; half < 2; ++half) {
-            if (half == 0 ? u0 : u1) continue;
-            call += "{ A f = g.m[" + N(half) + "]; " + guard + "pass_scale<T, " + N(J) + ", " + N(half) + ">(f, e, c, g.cm_reg); } ";
-          }
-        } else if (g.b0 == kTileOutside && !g.cm_lane) {
-          const std::string s0 = u0 ? "" : "pass_scale<T, 0, -1>(g.m[0], e, c, g.cm_reg);", s1 = u1 ? "" : "pass_scale<T, 0, -1>(g.m[1], e, c, g.cm_reg);";
-          call = "if ((base >> g.tpos_out) & 1ull) { " + s1 + " } else { " + s0 + " }";
-        } else {
-          call = std::string("const bool one = ") + (g.b0 == kTileOutside ? "((base >> g.tpos_out) & 1ull) != 0" : "((tb >> g.b0) & 1u) != 0") +
-                 "; A f = tile_sel(one, g.m[1], g.m[0]); " + guard + "pass_scale<T, 0, -1>(f, e, c, g.cm_reg);";
-        }
-      } else if (g.kind == 0) {
-        const int J = jof(g.b0);
-        call = g.cm_lane ? "pass_dense_lane<T, " + N(J) + ">(g, e, c, g.cm_reg, (tb & g.cm_lane) == g.cm_lane);"
-                         : "pass_dense<T, " + N(J) + ">(g, e, c, g.cm_reg);";
-      } else if (g.kind == 2) {
-        call = "pass_swap<T, " + N(jof(g.b0)) + ", " + N(jof(g.b1)) + ">(e, c, g.cm_reg, " + lane_args + ");";
-      } else if (g.kind == 3) {
-        call = matrix(16) + "pass_dense2<T, " + N(jof(g.b0)) + ", " + N(jof(g.b1)) + ">(M, e, c, g.cm_reg, " + lane_args + ");";
+      const TileGate<T>& g = gs[k].g;
+      w.gate_literal(gi, g);
+      std::string call = SegWriter<T>::gate_call(gs[k]);
+      const amp_t<T>* M = g.kind >= 3 ? plan.mats.data() + 16 * g.nz : nullptr;  // (the matrix of a dense 2- or 3-qubit gate)
+      if (g.kind == 3) {
+        call = w.matrix(M, 16) + "pass_dense2<T, " + N(jof(g.b0)) + ", " + N(jof(g.b1)) + ">(M, e, c, g.cm_reg, " + SegWriter<T>::kLaneArgs + ");";
       } else if (g.kind == 4 && dense3_inline) {
         // The same fold as pass_dense3w, written out for the (at most four) groups this gate really touches, every index a literal.
         // pass_dense3w's loop over the 32 elements is not unrolled by the compiler at NE = 32: `e` is indexed at run time and the whole
         // tile of the lane lives in a 528-byte stack object (profiles/r04_jit_segment_resources.txt: dense-k3 Grover on wide tiles).
         const int JA = jof(g.b0), JB = jof(g.b1), JC = jof(g.tpos_out);
-        call = matrix(64);
+        call = w.matrix(M, 64);
         for (int base = 0; base < 32; ++base) {
           if (((base >> JA) & 1) || ((base >> JB) & 1) || ((base >> JC) & 1)) continue;
-          uint32_t cb = 0;
-          for (int j = 0; j < kWideRegBits; ++j)
-            if ((base >> j) & 1) cb |= 1u << ps.R[j];
-          if ((cb & g.cm_reg) != g.cm_reg) continue;
+          if ((c[base] & g.cm_reg) != g.cm_reg) continue;
           auto idx = [&](int r) { return base | (((r >> 2) & 1) << JA) | (((r >> 1) & 1) << JB) | ((r & 1) << JC); };
           call += "{ const A x[8] = {";
           for (int r = 0; r < 8; ++r) call += "e[" + N(idx(r)) + "]" + (r < 7 ? ", " : "}; ");
@@ -1401,17 +1303,16 @@ static std::string wide_jit_source(const WidePlan<T>& plan, const Ins& ins, bool
           call += "} ";
         }
       } else if (g.kind == 4) {
-        call = matrix(64) + "pass_dense3w<T, " + N(jof(g.b0)) + ", " + N(jof(g.b1)) + ", " + N(jof(g.tpos_out)) + ">(M, e, c, g.cm_reg, " + lane_args + ");";
+        call = w.matrix(M, 64) + "pass_dense3w<T, " + N(jof(g.b0)) + ", " + N(jof(g.b1)) + ", " + N(jof(g.tpos_out)) + ">(M, e, c, g.cm_reg, " +
+               SegWriter<T>::kLaneArgs + ");";
       }
-      if (g.omask) L("      if ((base & g.omask) == g.omask) { " + call + " }");
-      else L("      { " + call + " }");
+      w.guarded(g, call);
       if (pin && (g.omask || call.compare(0, 9, "if ((base") == 0)) {
         std::string pl = "     ";
         for (int i = 0; i < 32; ++i) pl += " asm volatile(\"\" : \"+v\"(e[" + N(i) + "].x), \"+v\"(e[" + N(i) + "].y));";
         L(pl);
       }
-      L("      __builtin_amdgcn_sched_barrier(0);");
-      L("    }");
+      w.end_gate();
     }
     L("  }");
   }
@@ -1423,7 +1324,7 @@ static std::string wide_jit_source(const WidePlan<T>& plan, const Ins& ins, bool
     for (int u = 0; u < 32; ++u) L("  stg<NT>(st + (wbase | " + ub(u) + ") + lane_off, " + el + "[" + N(u) + "]);");
   }
   L("}");
-  return o;
+  return w.o;
 }
 
 // Look the segment's kernel up (compile it on a miss) and — unless `launch` is null (compile-only pass before a graph capture)
@@ -1756,13 +1657,110 @@ static int jit_compile_collected(qip_hip_state* s, std::vector<std::pair<std::st
   return QIP_OK;
 }
 
+// the Ins a tile kernel takes: the tile's high positions, and `extra` ones on top (controls taken off the grid, slice positions),
+// opened in the space where p5 and 5 have traded places (tile_block_base; p5 itself is a low position and never in `high`)
+static Ins tile_ins(const std::vector<uint32_t>& high, uint32_t p5, const std::vector<uint32_t>& extra = {}, uint64_t ormask = 0) {
+  std::vector<uint32_t> v = high;
+  v.insert(v.end(), extra.begin(), extra.end());
+  for (uint32_t& h : v)
+    if (h == 5u) h = p5;
+  return make_ins(v, ormask);
+}
+
+// How a sweep of either tile shape runs: whether it stores its tiles packed (`fold`, the batch's last step: BatchRun::fold_request
+// — the multi-GPU remap's gather rides in this sweep's store phase, TileStorePerm) and whether it runs in parts (`sl`: this step's
+// request, BatchRun::slice_first / slice_last).
+struct TileSweep {
+  bool folding = false;
+  TileSlicing* sl = nullptr;  // the accepted request to run in parts; null: one part
+  uint32_t nparts() const { return sl ? 1u << sl->nbits : 1u; }
+  uint64_t slice_or(uint32_t k) const {  // part k's bits at the slice positions
+    uint64_t v = 0;
+    for (uint32_t j = 0; sl && j < sl->nbits; ++j) v |= (uint64_t)((k >> j) & 1u) << sl->pos[j];
+    return v;
+  }
+};
+// `whole_grid`: the sweep may do either at all (an 11-bit sweep needs the pass kernel and every tile written: no blocks taken off
+// the grid).  An accepted slicing opens the slice positions in `ins` too.
+static int plan_sweep(qip_hip_state* s, const BatchRun& run, const TileStorePerm* fold, TileSlicing* sl, bool whole_grid, uint32_t tile_bits,
+                      const std::vector<uint32_t>& high, uint32_t p5, Ins* ins, TileSweep* f) {
+  // a packed store needs rows that stay rows (none of the gathered positions is a lane position of this tile) and the second
+  // buffer; otherwise the sweep runs as usual and the remap gathers by itself
+  bool folding = fold && fold->g && whole_grid && !s->capture_pool && !run.prepare();
+  if (folding)
+    for (uint32_t t = 0; t < fold->g; ++t) folding = folding && !tile_is_low(fold->sel[t], p5);
+  if (folding) QCHK(ensure_alt(s));
+  // r5: the sweep in 2^nbits parts (TileSlicing, qip_internal.h) — the slice positions must be block-index bits of this sweep
+  // (not tile positions, not positions taken off the grid), above the rows, and with `need_fold` the store must really be packed
+  bool slicing = sl && sl->nbits >= 1 && sl->nbits <= 3 && whole_grid && (!sl->need_fold || folding) && !(sl->in_place_only && folding) &&
+                 s->n >= tile_bits + sl->nbits;
+  if (slicing)
+    for (uint32_t j = 0; j < sl->nbits; ++j) {
+      slicing = slicing && sl->pos[j] > 11u && sl->pos[j] < s->n && !tile_is_low(sl->pos[j], p5) && std::find(high.begin(), high.end(), sl->pos[j]) == high.end();
+      for (uint32_t i = 0; i < j; ++i) slicing = slicing && sl->pos[i] != sl->pos[j];
+    }
+  if (slicing) *ins = tile_ins(high, p5, std::vector<uint32_t>(sl->pos, sl->pos + sl->nbits));
+  if (sl && !slicing && sl->fallback) QCHK(sl->fallback());
+  f->folding = folding;
+  f->sl = slicing ? sl : nullptr;
+  return QIP_OK;
+}
+// `launch(k)` for every part of the sweep, then what every sweep ends with: the profile record closes and a packed store makes the
+// second buffer current
+template <typename F>
+static int run_parts(qip_hip_state* s, const BatchRun& run, const TileSweep& f, ProfRec* rec, F&& launch) {
+  TileSlicing* sl = f.sl;
+  for (uint32_t k = 0; k < f.nparts(); ++k) {
+    if (sl && sl->before) QCHK(sl->before(k, f.folding));
+    QCHK(launch(k));
+    if (sl && sl->after) QCHK(sl->after(k, f.folding));
+    if (sl) sl->parts_done += 1;
+    if (sl && s->profile) s->prof_launches[KC_TILE_PARTS] += 1;
+  }
+  if (sl) sl->folded = f.folding;
+  if (s->profile) QCHK(prof_end(s, rec));
+  if (f.folding) {
+    std::swap(s->cur, s->alt);
+    std::swap(s->owns_cur, s->owns_alt);
+    if (run.fold_done) *run.fold_done = true;
+  }
+  return QIP_OK;
+}
+// A segment as its own kernel (either shape): looked up, and compiled on a miss, before the timed region starts; its numbers go to
+// the arena (nothing else is uploaded: the descriptors are constants of the code).  Arguments: the state, the tile count or the
+// part's slice bits, the parameters (`parametrised`), the packed-store destination.
+template <typename T>
+static int launch_compiled(qip_hip_state* s, const BatchRun& run, const TileSweep& f, const std::string& src, bool fma, bool parametrised,
+                           const std::vector<T>& params, uint64_t ntiles, uint32_t block, size_t lds, double sweep_bytes) {
+  QCHK(jit_get_and_launch(s, src, fma, nullptr, run.jit_collect));
+  if (run.prepare()) return QIP_OK;
+  if (!params.empty()) QCHK(arena_upload(s, params.data(), params.size() * sizeof(T), 0));
+  ProfRec rec;
+  rec.cls = KC_TILE_GATES;
+  if (s->profile) QCHK(prof_begin(s, KC_TILE_GATES, sweep_bytes, &rec));
+  void* st_ptr = s->cur;
+  uint64_t second_arg = ntiles;
+  void* params_ptr = s->arena;
+  void* out_ptr = s->alt;
+  // (a kernel without parameters has no third argument: the packed-store destination then comes third)
+  void* args_p[] = {&st_ptr, &second_arg, &params_ptr, &out_ptr};
+  void* args_np[] = {&st_ptr, &second_arg, &out_ptr};
+  void** args = (parametrised || !f.folding) ? args_p : args_np;
+  const dim3 grid = grid2d(ntiles >> (f.sl ? f.sl->nbits : 0), 1);
+  return run_parts(s, run, f, &rec, [&](uint32_t k) -> int {
+    if (f.sl) second_arg = f.slice_or(k);
+    return jit_get_and_launch(s, src, fma, [&](hipFunction_t fn) -> int {
+      HIPCHK(hipModuleLaunchKernel(fn, grid.x, grid.y, 1, block, 1, 1, (unsigned)lds, s->stream, args, nullptr));
+      return QIP_OK;
+    });
+  });
+}
+
 template <typename T>
 static int launch_tile_segment(qip_hip_state* s, const BatchRun& run, const std::vector<const TileItem*>& seg,
                                std::vector<uint32_t> high_in, const TileStorePerm* fold = nullptr, TileSlicing* sl = nullptr,
                                uint32_t p5_override = 0, const std::vector<uint32_t>* grid_ctl = nullptr, double alg_bytes = 0) {
-  // `fold` (the batch's last step: BatchRun::fold_request): store the tiles into the second buffer, packed for the multi-GPU
-  // exchange (TileStorePerm), and make that buffer current — the remap's gather rides in this sweep's store phase instead of
-  // costing a sweep of its own.  `sl`: this step's request to run in parts (BatchRun::slice_first / slice_last)
+  // `fold`, `sl`: see TileSweep.
   // `grid_ctl` (one-op sweeps): control positions OUTSIDE the tile that are taken off the grid — only the blocks whose base
   // reads 1 there are launched, so a controlled gate sweeps half / a quarter of the vector like the dedicated kernels do
   // (the kernel's own test of `omask` against the block's base then always passes).  `alg_bytes`: what the profile credits.
@@ -1799,70 +1797,18 @@ static int launch_tile_segment(qip_hip_state* s, const BatchRun& run, const std:
   d.p5 = plan.p5;
   Ins ins = tile_ins(high, plan.p5);  // (sorts its own copy; `high` keeps the tile-bit order)
   uint64_t ntiles = 1ull << (s->n - kTileBits);
-  if (grid_ctl && !grid_ctl->empty()) {
-    std::vector<uint32_t> opened = high, ctl = *grid_ctl;
-    for (uint32_t c : ctl) opened.push_back(c);
-    for (uint32_t& o : opened)
-      if (o == 5u) o = plan.p5;  // (tile_block_base: the space where p5 and 5 have traded places)
+  const bool whole_grid = !grid_ctl || grid_ctl->empty();
+  if (!whole_grid) {
     uint64_t ones = 0;
-    for (uint32_t c : ctl) ones |= 1ull << (c == 5u ? plan.p5 : c);
-    ins = make_ins(opened, ones);
-    ntiles >>= ctl.size();
+    for (uint32_t c : *grid_ctl) ones |= 1ull << (c == 5u ? plan.p5 : c);
+    ins = tile_ins(high, plan.p5, *grid_ctl, ones);
+    ntiles >>= grid_ctl->size();
   }
   const double sweep_bytes = alg_bytes > 0 ? alg_bytes : 2.0 * (double)s->amp_bytes * (double)s->namps;
-  // a packed store needs every tile written (no blocks taken off the grid), the pass kernel, rows that stay rows (none of
-  // the gathered positions is a lane position of this tile) and the second buffer; otherwise the sweep runs as usual and the
-  // remap gathers by itself
-  bool folding = fold && fold->g && s->tile_passes && (!grid_ctl || grid_ctl->empty()) && !s->capture_pool && !run.prepare();
-  if (folding)
-    for (uint32_t t = 0; t < fold->g; ++t) folding = folding && !tile_is_low(fold->sel[t], plan.p5);
-  if (folding) QCHK(ensure_alt(s));
-  // r5: the sweep in 2^nbits parts (TileSlicing, qip_internal.h) — the slice positions must be block-index bits of this sweep
-  // (not tile positions, not positions taken off the grid), above the rows, and with `need_fold` the store must really be packed
-  bool slicing = sl && sl->nbits >= 1 && sl->nbits <= 3 && s->tile_passes && (!grid_ctl || grid_ctl->empty()) && (!sl->need_fold || folding) &&
-                 !(sl->in_place_only && folding) && s->n >= (uint32_t)kTileBits + sl->nbits;
-  if (slicing)
-    for (uint32_t j = 0; j < sl->nbits; ++j) {
-      slicing = slicing && sl->pos[j] > 11u && sl->pos[j] < s->n && !tile_is_low(sl->pos[j], plan.p5) &&
-                std::find(high.begin(), high.end(), sl->pos[j]) == high.end();
-      for (uint32_t i = 0; i < j; ++i) slicing = slicing && sl->pos[i] != sl->pos[j];
-    }
-  Ins ins_sliced = ins;
-  if (slicing) {
-    std::vector<uint32_t> opened = high;
-    for (uint32_t& o : opened)
-      if (o == 5u) o = plan.p5;  // (as above: the space where p5 and 5 have traded places; slice positions are > 11)
-    for (uint32_t j = 0; j < sl->nbits; ++j) opened.push_back(sl->pos[j]);
-    ins_sliced = make_ins(opened, 0);
-  }
-  const uint32_t nparts = slicing ? 1u << sl->nbits : 1u;
-  auto slice_or = [&](uint32_t k) {
-    uint64_t v = 0;
-    for (uint32_t j = 0; slicing && j < sl->nbits; ++j) v |= (uint64_t)((k >> j) & 1u) << sl->pos[j];
-    return v;
-  };
-  if (sl && !slicing && sl->fallback) QCHK(sl->fallback());
-  auto folded_swap = [&]() {
-    std::swap(s->cur, s->alt);
-    std::swap(s->owns_cur, s->owns_alt);
-    if (run.fold_done) *run.fold_done = true;
-  };
+  TileSweep f;
+  QCHK(plan_sweep(s, run, fold, sl, s->tile_passes && whole_grid, kTileBits, high, plan.p5, &ins, &f));
   const size_t lds = sizeof(amp_t<T>) << kTileBits;
-  const TileGate<T>* dg = nullptr;  // device addresses: valid only after the upload (the arena may grow / move)
-  const amp_t<T>* dmats = nullptr;
-  const TileDiagItem<T>* ditems = nullptr;
-  ProfRec rec;
-  rec.cls = KC_TILE_GATES;
-  auto begin = [&]() -> int {  // descriptors up, then the timed region starts
-    QCHK(upload_gates());
-    dg = (const TileGate<T>*)s->arena;
-    dmats = (const amp_t<T>*)((const char*)s->arena + gates_bytes);
-    ditems = (const TileDiagItem<T>*)((const char*)s->arena + items_off);
-    if (s->profile) QCHK(prof_begin(s, KC_TILE_GATES, sweep_bytes, &rec));
-    return QIP_OK;
-  };
   if (s->tile_passes && run.tile_jit) {
-    // the segment as its own kernel: nothing to upload, the descriptors are constants of the code
     const bool fma = s->tile_fma && run.tile >= 2;  // tile = 1 promises IEEE equality with the gate-by-gate path: never fused
     // structure compiled, numbers in the arena (see tile_jit_source): the default form.  tile_jit = 3 (tuning aid) writes the
     // numbers into the source as literals instead: every constant then occupies vector registers (gfx950's VOP3 takes no
@@ -1886,47 +1832,24 @@ static int launch_tile_segment(qip_hip_state* s, const BatchRun& run, const std:
       if (nb < 3) remap = 0;
       else remap = 16 + (int)std::min(J, nb - 3);
     }
-    if (slicing) remap = 0;
-    const std::string src = tile_jit_source<T>(plan, slicing ? ins_sliced : ins, use_nt(s), remap, parametrised ? &params : nullptr, merge,
-                                               folding ? fold : nullptr, slicing);
-    QCHK(jit_get_and_launch(s, src, fma, nullptr, run.jit_collect));  // compile on a miss BEFORE the timed region starts
-    if (run.prepare()) return QIP_OK;
-    if (parametrised && !params.empty()) QCHK(arena_upload(s, params.data(), params.size() * sizeof(T), 0));
-    if (s->profile) QCHK(prof_begin(s, KC_TILE_GATES, sweep_bytes, &rec));
-    void* st_ptr = s->cur;
-    uint64_t ntiles_arg = ntiles;  // (a sliced kernel reads the part's slice bits here instead)
-    void* params_ptr = s->arena;
-    void* out_ptr = s->alt;
-    // (a kernel without parameters has no third argument: the packed-store destination then comes third)
-    void* args_p[] = {&st_ptr, &ntiles_arg, &params_ptr, &out_ptr};
-    void* args_np[] = {&st_ptr, &ntiles_arg, &out_ptr};
-    void** args = (parametrised || !folding) ? args_p : args_np;
-    const dim3 grid = grid2d(ntiles >> (slicing ? sl->nbits : 0), 1);
-    for (uint32_t k = 0; k < nparts; ++k) {
-      if (slicing && sl->before) QCHK(sl->before(k, folding));
-      if (slicing) ntiles_arg = slice_or(k);
-      QCHK(jit_get_and_launch(s, src, fma, [&](hipFunction_t fn) -> int {
-        HIPCHK(hipModuleLaunchKernel(fn, grid.x, grid.y, 1, kTileBlock, 1, 1, (unsigned)lds, s->stream, args, nullptr));
-        return QIP_OK;
-      }));
-      if (slicing && sl->after) QCHK(sl->after(k, folding));
-      if (slicing) sl->parts_done += 1;
-      if (slicing && s->profile) s->prof_launches[KC_TILE_PARTS] += 1;
-    }
-    if (slicing) sl->folded = folding;
-    if (s->profile) QCHK(prof_end(s, &rec));
-    if (folding) folded_swap();
-    return QIP_OK;
+    if (f.sl) remap = 0;
+    const std::string src = tile_jit_source<T>(plan, ins, use_nt(s), remap, parametrised ? &params : nullptr, merge, f.folding ? fold : nullptr, f.sl != nullptr);
+    return launch_compiled<T>(s, run, f, src, fma, parametrised, params, ntiles, kTileBlock, lds, sweep_bytes);
   }
   if (run.prepare()) return QIP_OK;
+  QCHK(upload_gates());  // descriptors up, then the timed region starts
+  const TileGate<T>* dg = (const TileGate<T>*)s->arena;  // device addresses: valid only after the upload (the arena may grow / move)
+  const amp_t<T>* dmats = (const amp_t<T>*)((const char*)s->arena + gates_bytes);
+  const TileDiagItem<T>* ditems = (const TileDiagItem<T>*)((const char*)s->arena + items_off);
+  ProfRec rec;
+  rec.cls = KC_TILE_GATES;
+  if (s->profile) QCHK(prof_begin(s, KC_TILE_GATES, sweep_bytes, &rec));
   if (s->tile_passes) {
-    QCHK(begin());
-    const uint64_t ntiles_part = ntiles >> (slicing ? sl->nbits : 0);
-    for (uint32_t k = 0; k < nparts; ++k) {
-      Ins ins_k = slicing ? ins_sliced : ins;
-      ins_k.ormask |= slice_or(k);
-      if (slicing && sl->before) QCHK(sl->before(k, folding));
-      if (folding) {
+    const uint64_t ntiles_part = ntiles >> (f.sl ? f.sl->nbits : 0);
+    return run_parts(s, run, f, &rec, [&](uint32_t k) -> int {
+      Ins ins_k = ins;
+      ins_k.ormask |= f.slice_or(k);
+      if (f.folding) {
 #define TPF(NTV) hipLaunchKernelGGL((k_tile_passes<T, NTV, true>), grid2d(ntiles_part, 1), dim3(kTileBlock), lds, s->stream, \
                                     (amp_t<T>*)s->cur, ins_k, pd, dg, dmats, (amp_t<T>*)s->alt, *fold, ditems)
         if (use_nt(s)) TPF(true);
@@ -1940,25 +1863,13 @@ static int launch_tile_segment(qip_hip_state* s, const BatchRun& run, const std:
 #undef TP
       }
       HIPCHK(hipGetLastError());
-      if (slicing && sl->after) QCHK(sl->after(k, folding));
-      if (slicing) sl->parts_done += 1;
-      if (slicing && s->profile) s->prof_launches[KC_TILE_PARTS] += 1;
-    }
-    if (slicing) sl->folded = folding;
-    if (folding) {
-      if (s->profile) QCHK(prof_end(s, &rec));
-      folded_swap();
       return QIP_OK;
-    }
-  } else {
-    QCHK(begin());
-    if (use_nt(s))
-      hipLaunchKernelGGL((k_tile_gates<T, true>), grid2d(ntiles, 1), dim3(kBlock), lds, s->stream,
-                         (amp_t<T>*)s->cur, ins, d, dg);
-    else
-      hipLaunchKernelGGL((k_tile_gates<T, false>), grid2d(ntiles, 1), dim3(kBlock), lds, s->stream,
-                         (amp_t<T>*)s->cur, ins, d, dg);
+    });
   }
+  if (use_nt(s))
+    hipLaunchKernelGGL((k_tile_gates<T, true>), grid2d(ntiles, 1), dim3(kBlock), lds, s->stream, (amp_t<T>*)s->cur, ins, d, dg);
+  else
+    hipLaunchKernelGGL((k_tile_gates<T, false>), grid2d(ntiles, 1), dim3(kBlock), lds, s->stream, (amp_t<T>*)s->cur, ins, d, dg);
   HIPCHK(hipGetLastError());
   if (s->profile) QCHK(prof_end(s, &rec));
   return QIP_OK;
@@ -1971,80 +1882,18 @@ static int launch_wide_segment(qip_hip_state* s, const BatchRun& run, const std:
   arena_begin_group(s);
   WidePlan<T> plan;
   QCHK(build_wide_segment<T>(s->n, seg, std::move(high_in), &plan, run.tile >= 2 ? 2 : 1));
-  const Ins ins = tile_ins(plan.high, plan.p5);
-  const bool fma = s->tile_fma && run.tile >= 2;
+  Ins ins = tile_ins(plan.high, plan.p5);
+  TileSweep f;
+  QCHK(plan_sweep(s, run, fold, sl, true, kWideBits, plan.high, plan.p5, &ins, &f));
   const bool parametrised = run.tile_jit != 3;
   std::vector<T> params;
   const bool merge = s->tile_merge && run.tile >= 2;  // products of runs of diagonal gates: rounding differs (1e-12 mode only)
-  // r5: a packed store (the multi-GPU remap's gather rides in this sweep, TileStorePerm) under the same conditions as the 11-bit
-  // sweeps: none of the gathered positions is a lane position of the tile, the second buffer exists
-  bool folding = fold && fold->g && !s->capture_pool && !run.prepare();
-  if (folding)
-    for (uint32_t t = 0; t < fold->g; ++t) folding = folding && !tile_is_low(fold->sel[t], plan.p5);
-  if (folding) QCHK(ensure_alt(s));
-  // r5: the sweep in parts (TileSlicing: the sharded state's exchange overlaps with it)
-  bool slicing = sl && sl->nbits >= 1 && sl->nbits <= 3 && (!sl->need_fold || folding) && !(sl->in_place_only && folding) &&
-                 s->n >= (uint32_t)kWideBits + sl->nbits;
-  if (slicing)
-    for (uint32_t j = 0; j < sl->nbits; ++j) {
-      slicing = slicing && sl->pos[j] > 11u && sl->pos[j] < s->n && !tile_is_low(sl->pos[j], plan.p5) &&
-                std::find(plan.high.begin(), plan.high.end(), sl->pos[j]) == plan.high.end();
-      for (uint32_t i = 0; i < j; ++i) slicing = slicing && sl->pos[i] != sl->pos[j];
-    }
-  Ins ins_use = ins;
-  if (slicing) {
-    std::vector<uint32_t> opened = plan.high;
-    for (uint32_t& o : opened)
-      if (o == 5u) o = plan.p5;
-    for (uint32_t j = 0; j < sl->nbits; ++j) opened.push_back(sl->pos[j]);
-    ins_use = make_ins(opened, 0);
-  }
-  if (sl && !slicing && sl->fallback) QCHK(sl->fallback());
-  const std::string src = wide_jit_source<T>(plan, ins_use, use_nt(s), parametrised ? &params : nullptr, merge, g_tile_wide_pin != 0, g_tile_wide_dense3_inline != 0, slicing,
-                                             folding ? fold : nullptr);
+  const std::string src = wide_jit_source<T>(plan, ins, use_nt(s), parametrised ? &params : nullptr, merge, g_tile_wide_pin != 0, g_tile_wide_dense3_inline != 0,
+                                             f.sl != nullptr, f.folding ? fold : nullptr);
   if (src.empty()) return fail(QIP_ERR_INVALID, "internal: wide segment source");
-  QCHK(jit_get_and_launch(s, src, fma, nullptr, run.jit_collect));  // compile on a miss before the timed region starts
-  if (run.prepare()) return QIP_OK;
-  if (parametrised && !params.empty()) QCHK(arena_upload(s, params.data(), params.size() * sizeof(T), 0));
-  ProfRec rec;
-  rec.cls = KC_TILE_GATES;
-  if (s->profile) QCHK(prof_begin(s, KC_TILE_GATES, 2.0 * (double)s->amp_bytes * (double)s->namps, &rec));
-  void* st_ptr = s->cur;
-  const uint64_t ntiles = (1ull << (s->n - (uint32_t)kWideBits)) >> (slicing ? sl->nbits : 0);
-  uint64_t second_arg = ntiles;  // (a sliced kernel reads the part's slice bits here)
-  void* params_ptr = s->arena;
-  void* out_ptr = s->alt;
-  // (a kernel without parameters has no third argument: the packed-store destination then comes third)
-  void* args_p[] = {&st_ptr, &second_arg, &params_ptr, &out_ptr};
-  void* args_np[] = {&st_ptr, &second_arg, &out_ptr};
-  void** args = (parametrised || !folding) ? args_p : args_np;
-  const dim3 grid = grid2d(ntiles, 1);
   const size_t lds = 2 * (sizeof(amp_t<T>) << kTileBits);  // the transposition buffer: two quarters of the tile
-  const uint32_t nparts = slicing ? 1u << sl->nbits : 1u;
-  for (uint32_t k = 0; k < nparts; ++k) {
-    if (slicing) {
-      second_arg = 0;
-      for (uint32_t j = 0; j < sl->nbits; ++j) second_arg |= (uint64_t)((k >> j) & 1u) << sl->pos[j];
-      if (sl->before) QCHK(sl->before(k, folding));
-    }
-    QCHK(jit_get_and_launch(s, src, fma, [&](hipFunction_t fn) -> int {
-      HIPCHK(hipModuleLaunchKernel(fn, grid.x, grid.y, 1, 256, 1, 1, (unsigned)lds, s->stream, args, nullptr));
-      return QIP_OK;
-    }));
-    if (slicing) {
-      if (sl->after) QCHK(sl->after(k, folding));
-      sl->parts_done += 1;
-      if (s->profile) s->prof_launches[KC_TILE_PARTS] += 1;
-    }
-  }
-  if (slicing) sl->folded = folding;
-  if (s->profile) QCHK(prof_end(s, &rec));
-  if (folding) {
-    std::swap(s->cur, s->alt);
-    std::swap(s->owns_cur, s->owns_alt);
-    if (run.fold_done) *run.fold_done = true;
-  }
-  return QIP_OK;
+  return launch_compiled<T>(s, run, f, src, s->tile_fma && run.tile >= 2, parametrised, params, 1ull << (s->n - (uint32_t)kWideBits), 256, lds,
+                            2.0 * (double)s->amp_bytes * (double)s->namps);
 }
 
 template <typename T>
@@ -2148,11 +1997,7 @@ static int debug_jit_t(int dtype, uint32_t n, const qip_op* ops, uint64_t count,
       sp->g = 1;
       sp->Lg = n - 1;
       sp->sel[0] = sp->sel_desc[0] = spare[0];
-      std::vector<uint32_t> opened = high;
-      for (uint32_t& o : opened)
-        if (o == 5u) o = p5;
-      opened.push_back(spare[1]);
-      *ins = make_ins(opened, 0);
+      *ins = tile_ins(high, p5, {spare[1]});
       return true;
     };
     if ((mode & 16) && n > (uint32_t)kWideBits) {  // mode bit 4: wide tiles

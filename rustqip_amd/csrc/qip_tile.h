@@ -86,8 +86,6 @@ template <typename T> static inline uint32_t tile_p5_of(uint32_t n) { return til
 static inline bool tile_is_low(uint32_t pos, uint32_t p5) { return pos < 5u || pos == p5; }
 static inline uint32_t tile_low_bit(uint32_t pos) { return pos < 5u ? pos : 5u; }  // (only for positions that are low)
 static inline uint64_t tile_low_mask(uint32_t p5) { return 31ull | (1ull << p5); }
-// the Ins a tile kernel takes: the high positions opened in the space where p5 and 5 have traded places
-Ins tile_ins(const std::vector<uint32_t>& high, uint32_t p5);
 
 // ---- wide tiles (r4, option "tile_wide"): 2^13 amplitudes per block held in REGISTERS (32 per lane = five register bits),
 // seven free positions per sweep; LDS is a 32-KiB transposition buffer.  Run-time-compiled segments only.

@@ -157,13 +157,6 @@ extern "C" int qip_hip_tile_lane_assignment(int dtype, const uint32_t* pass_bits
 } QIP_CATCH_ALL
 
 
-Ins tile_ins(const std::vector<uint32_t>& high, uint32_t p5) {
-  std::vector<uint32_t> v = high;
-  for (uint32_t& h : v)
-    if (h == 5u) h = p5;  // (p5 itself is a low position and never in `high`)
-  return make_ins(v, 0);
-}
-
 template <typename T>
 int build_tile_segment(uint32_t n, bool passes, const std::vector<const TileItem*>& seg_in,
                               std::vector<uint32_t> high, TileSegmentPlan<T>* out, int order_rule, uint32_t p5_override) {
