@@ -12,8 +12,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 # one translation unit per concern (csrc/qip_internal.h lists them); compiled in parallel, linked into ONE library whose
 # only exports are the C ABI (csrc/exports.map)
-UNITS = ["qip_core", "qip_launch", "qip_tile_sched", "qip_circuit", "qip_host", "qip_measure", "qip_dist"]
-HEADERS = [os.path.join(CSRC, h) for h in ("qip_kernels.h", "qip_internal.h", "qip_tile.h")] + [
+UNITS = ["qip_core", "qip_launch", "qip_tile_sched", "qip_circuit", "qip_jit", "qip_host", "qip_measure", "qip_dist"]
+HEADERS = [os.path.join(CSRC, h) for h in ("qip_kernels.h", "qip_internal.h", "qip_jit.h", "qip_tile.h")] + [
     os.path.join(HERE, "..", "include", "qip_hip.h"), os.path.join(HERE, "..", "include", "qip_hip_debug.h")]
 OBJDIR = os.path.join(HERE, "build")
 OUT = os.path.join(HERE, "lib", "libqip_hip.so")
@@ -29,7 +29,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fn
 if os.environ.get("QIP_HIP_TUNING"):
     FLAGS.append("-DQIP_HIP_TUNING")
 LINK = ["--offload-arch=gfx950", "-fPIC", "-shared", "-Wl,--version-script=" + os.path.join(CSRC, "exports.map")]
-LIBS = ["-ldl"]  # librccl and libhiprtc are dlopen-ed on first use (qip_dist.hip, qip_circuit.hip): no link-time dependency
+LIBS = ["-ldl"]  # librccl and libhiprtc are dlopen-ed on first use (qip_dist.hip, qip_jit.hip): no link-time dependency
 
 EMBED = os.path.join(CSRC, "qip_kernels_embed.inc")
 
@@ -64,7 +64,7 @@ def build(force: bool = False) -> str:
     jobs = []
     for u in UNITS:
         src, obj = os.path.join(CSRC, u + ".hip"), os.path.join(OBJDIR, u + ".o")
-        deps = [src] + HEADERS + ([EMBED] if u == "qip_circuit" else [])
+        deps = [src] + HEADERS + ([EMBED] if u == "qip_jit" else [])
         if force or _stale(obj, deps):
             jobs.append([HIPCC, *FLAGS, "-c", src, "-o", obj])
     if jobs:

@@ -88,11 +88,6 @@ extern "C" int qip_hip_set_global_option(const char* key, int64_t value) try {
     return QIP_OK;
   }
   if (!strcmp(key, "tile_diag_runs")) { g_tile_diag_runs = value != 0; return QIP_OK; }
-  if (!strcmp(key, "jit_threads")) {
-    if (value < 1 || value > 64) return fail(QIP_ERR_INVALID, "jit_threads must be 1..64");
-    g_jit_threads = value;
-    return QIP_OK;
-  }
   if (!strcmp(key, "tile_row_split_f32")) {
     if (value != 5 && value != 12) return fail(QIP_ERR_INVALID, "tile_row_split_f32 is 12 (split rows) or 5 (contiguous rows)");
     g_tile_row_split_f32 = value;

@@ -2,7 +2,8 @@
 //   qip_core.hip      errors, options, op flattening / validation, kernel choice (make_plan), state handles, profiling
 //   qip_launch.hip    one launcher per kernel class, apply_op
 //   qip_tile_sched.hip the host-only tile scheduler (segments, passes, relabelling, plan export)
-//   qip_circuit.hip   apply_ops: fusion, tile sweeps (interpreter + run-time-compiled segments), hipGraph programs
+//   qip_circuit.hip   apply_ops: fusion, tile sweeps (interpreter + the source of run-time-compiled segments), hipGraph programs
+//   qip_jit.hip       the run-time compiler behind qip_jit.h: hiprtc, disk cache, helper processes, resident kernels, plan memo
 //   qip_host.hip      host-pointer twins of the reference functions
 //   qip_measure.hip   measurement
 //   qip_dist.hip      the sharded state (planner, pack sweep, exchange)
@@ -30,6 +31,7 @@
 #include "../../include/qip_hip.h"
 #include "../../include/qip_hip_debug.h"
 #include "qip_kernels.h"
+#include "qip_jit.h"
 
 using namespace qipk;
 
@@ -67,9 +69,7 @@ extern int64_t g_collective_timeout_s;             // qip_core.hip: seconds a ra
 extern int64_t g_sparse_tile;  // qip_launch.hip
 extern int64_t g_soft_measure_one_pass;  // qip_measure.hip
 extern int64_t g_tile_wide_pin, g_tile_wide_dense3_inline;  // qip_circuit.hip
-extern int64_t g_jit_disk, g_jit_procs, g_jit_world;  // qip_circuit.hip: code objects on disk, helper processes, ranks sharing the host
 extern int64_t g_debug_slice_sweeps;  // qip_circuit.hip
-extern int64_t g_jit_threads;     // qip_circuit.hip: host threads that compile a plan's new segments side by side
 extern int64_t g_force_k4_direct;  // tuning aid: dense k = 4 on the matrix cores reads its operands straight from HBM (k_gate_kq_mfma)  // 0 = never, 1 = single dense k = 2, 3 / Swap ops with a bit inside a row go as a one-item tile sweep, 2 = every dense k = 2, 3  // tuning aids of the tile sweeps (qip_hip_set_global_option)
 
 struct FlatOp {
@@ -230,10 +230,9 @@ struct BatchRun {
   // kLookupOnly (r6, option tile_auto, one-shot callers): the plan's segments are only LOOKED UP (memory, disk cache); a miss
   // hands them to background helpers and the batch returns kJitMiss before anything has run.
   enum Jit { kRun, kPrepare, kLookupOnly } jit = kRun;
-  // r4 (kPrepare): the sources of a plan's segments that are not in the kernel cache yet (source text, contraction flag) are
-  // collected here instead of compiled; apply_ops compiles them on several host threads before the first launch (hiprtc:
-  // ~0.35 s per 11-bit segment, ~1.4 s per wide one)
-  std::vector<std::pair<std::string, bool>>* jit_collect = nullptr;
+  // r4 (kPrepare): the segments of a plan that are not in the kernel cache yet are collected here instead of compiled; apply_ops
+  // has them compiled side by side before the first launch (jit_prepare; hiprtc: ~0.35 s per 11-bit segment, ~1.4 s per wide one)
+  std::vector<JitJob>* jit_collect = nullptr;
   // The sharded state's remap (qip_dist.hip) asks the batch it hands to this shard to leave its result PACKED in the second
   // buffer (TileStorePerm: the leaving qubits' positions gathered on top): the last sweep of the batch — if it is a tile
   // sweep — stores its tiles there and the remap needs no gather sweep of its own.  The step loop hands the request to the
@@ -263,9 +262,6 @@ static inline void arena_begin_group(qip_hip_state* s) {
 int ensure_partial(qip_hip_state* s, size_t count);
 int ensure_alt(qip_hip_state* s);
 void programs_orphan(qip_hip_state* s);  // qip_circuit.hip
-int jit_set_cache_cap(int64_t cap);      // qip_circuit.hip (global option "jit_cache_cap")
-int jit_set_disk_cap_mb(int64_t mb);     // qip_circuit.hip (global option "jit_disk_cap_mb")
-uint64_t jit_cache_generation();
 // qip_circuit.hip: `op` as a one-item tile sweep; *done = false when it is not a tile item (nothing launched)
 template <typename T>
 int tile_apply_single(qip_hip_state* s, const BatchRun& run, const qip_op* op, const TileStorePerm* fold, bool* done, double alg_bytes);
