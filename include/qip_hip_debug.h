@@ -32,7 +32,12 @@ int qip_hip_tile_lane_assignment(int dtype, const uint32_t* pass_bits, uint64_t*
  * the calling thread's next call; NULL on error): the schedule of qip_hip_plan_tiles and, for every multi-gate
  * step, the free bit positions, the passes (exchange bits, lane-bit assignment) and the gate descriptors exactly
  * as they are shipped to k_tile_passes.  tests/test_tile_plan_cpu.py replays it with a numpy model of the kernel
- * and checks the result against the CPU oracle, so the host half of the tile path is covered without a GPU. */
+ * and checks the result against the CPU oracle, so the host half of the tile path is covered without a GPU.
+ * Mode bits on top of the schedule mode: 1024 adds, per multi-gate step, "interp": the form the interpreter kernel takes
+ * runs of diagonal gates in; 4096 adds "absorb": what the interpreter kernel is really handed for the step — the item list
+ * with its uncontrolled X gates absorbed into their neighbours, that list's order, passes, gates, matrices and runs (the keys
+ * of a step), "flip" (tile-index bits the store flips; "flip_pos": the same as amplitude-index positions) and "dropped"
+ * (items that left the list).  Without a bit the output is what it was without it. */
 const char* qip_hip_debug_tile_plan(int dtype, uint32_t n, const qip_op* ops, uint64_t count, int mode);
 
 /* Host-only test hook (r4): what the host decides about applying ONE SparseMatrix op in place through the LDS-staged tile

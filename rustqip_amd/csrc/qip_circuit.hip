@@ -830,7 +830,13 @@ static int launch_tile_segment(qip_hip_state* s, const BatchRun& run, const std:
   // (the kernel's own test of `omask` against the block's base then always passes).  `alg_bytes`: what the profile credits.
   arena_begin_group(s);
   TileSegmentPlan<T> plan;
-  QCHK(build_tile_segment<T>(s->n, s->tile_passes != 0, seg, std::move(high_in), &plan, run.tile >= 2 ? 2 : 1, p5_override));
+  // a multi-gate sweep of the interpreter kernel: its uncontrolled X gates go into their neighbours and into the store's flip
+  // (tile_absorb_x) before the passes are laid out.  Compiled segments, k_tile_gates and the one-op sweeps take the list as it is
+  TileAbsorbedX absorbed;
+  if (s->tile_passes && !run.tile_jit && !grid_ctl && !p5_override)
+    QCHK(build_tile_segment_absorbed<T>(s->n, seg, std::move(high_in), &plan, run.tile >= 2 ? 2 : 1, &absorbed));
+  else
+    QCHK(build_tile_segment<T>(s->n, s->tile_passes != 0, seg, std::move(high_in), &plan, run.tile >= 2 ? 2 : 1, p5_override));
   const std::vector<uint32_t>& high = plan.high;
   // r5: the interpreter kernel takes runs of diagonal gates as one loop over TileDiagItem steps (tile_merge_diag_runs: the same
   // products in the same order, without the per-gate decoding); the plan itself stays what the generators and the CPU replay read

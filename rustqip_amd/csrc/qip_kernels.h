@@ -1689,7 +1689,9 @@ struct TilePassDesc {
   uint32_t npasses;
   uint32_t hpos[kTileHigh];
   uint32_t p5;  // amplitude-index position of tile bit 5 (see tile_block_base)
-  uint32_t pad_;
+  // tile-index bits the STORE flips: the amplitude stored at tile index t is the one the passes left at t ^ flip.  The uncontrolled
+  // X gates of an interpreter launch that the host could push to the end of the segment (tile_absorb_x) end up here; 0 otherwise
+  uint32_t flip;
   TilePass pass[kTileMaxPasses];
 };
 
@@ -1707,6 +1709,13 @@ struct TilePassDesc {
 //   * a diagonal gate whose target is a pass bit has a wave-uniform factor per element (unit factors skipped by
 //     a scalar branch); on a lane bit the factor is selected once per gate, not per element;
 //   * X is a register exchange; gates with real entries multiply two reals per product;
+//   * an uncontrolled X is mostly not in the gate list at all (interpreter launches; tile_absorb_x on the host): a register exchange
+//     is no arithmetic but it is a descriptor fetch, a jump and the compiler's register ping-pong — two thirds of a Hadamard.
+//     X on a tile bit is a fixed permutation of the tile, so the host pushes it forward through the later gates (a dense gate on the
+//     same bit takes it as a column swap, a diagonal one as an entry swap, a control makes it reappear) and what is still pending
+//     at the end of the segment is `d.flip`: the store reads LDS at slot(t ^ flip) = slot(t) ^ slot(flip), one wave-uniform XOR.
+//     The flip is an involution of the tile, so the sweep stays in place, and XOR-ing every lane's slot with one constant keeps
+//     the access as conflict-free as it was;
 //   * the reference's leading "0 +" of every row sum is dropped: 0 + p == p under IEEE == (it only turns a -0
 //     into +0), the same equality the X and real-entry forms rely on;
 //   * explicit FMAs for tile = 2 (which is held to 1e-12 anyway) would halve the arithmetic, but every FMA
@@ -2112,12 +2121,13 @@ __global__ __launch_bounds__(kTileBlock, 5) void k_tile_passes(amp_t<T>* __restr
     __syncthreads();
   }
   {
+    const uint32_t slot_src = slot_tid ^ tile_slot<A>(d.flip & ((1u << kTileBits) - 1u));  // (slot() is linear over XOR)
 #pragma unroll
     for (int u = 0; u < PER; ++u) {
       const uint64_t ub = wbase | ((uint64_t)(u & 1) << d.hpos[kTileWaveBits]) | ((uint64_t)((u >> 1) & 1) << d.hpos[kTileWaveBits + 1]) |
                           ((uint64_t)((u >> 2) & 1) << d.hpos[kTileWaveBits + 2]);
-      if constexpr (FOLD) stg<NT>(out + tile_packed_index(ub, sp) + tile_packed_index(lane_off, sp), tile[slot_tid ^ tile_slot<A>((uint32_t)u << kTileLaneBits)]);
-      else stg<NT>(st + ub + lane_off, tile[slot_tid ^ tile_slot<A>((uint32_t)u << kTileLaneBits)]);
+      if constexpr (FOLD) stg<NT>(out + tile_packed_index(ub, sp) + tile_packed_index(lane_off, sp), tile[slot_src ^ tile_slot<A>((uint32_t)u << kTileLaneBits)]);
+      else stg<NT>(st + ub + lane_off, tile[slot_src ^ tile_slot<A>((uint32_t)u << kTileLaneBits)]);
     }
   }
 }

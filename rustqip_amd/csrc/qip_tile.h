@@ -49,6 +49,23 @@ template <typename T> struct TileInterpPlan {
 template <typename T> void tile_merge_diag_runs(const TileSegmentPlan<T>& plan, TileInterpPlan<T>* out, uint32_t min_run = 2);
 extern int64_t g_tile_diag_runs;  // global option "tile_diag_runs" (1 = on)
 
+// A segment's item list with its uncontrolled X gates absorbed (INTERPRETER launches only, like the diagonal runs: plans, the
+// generators, the one-op sweeps and the wide path never see it).  Every X target of a segment is a tile position, so X is a fixed
+// permutation of the tile that can be pushed forward through the later items; what is still pending at the end is `flip`, which
+// the kernel's store applies for nothing (TilePassDesc::flip).  `seg` points into the caller's items and into `owned`.
+struct TileAbsorbedX {
+  std::vector<const TileItem*> seg;  // the reduced list: build_tile_segment's input
+  std::deque<TileItem> owned;        // items that were rewritten (M -> M.X, swapped diagonal entries) or put back (explicit X)
+  uint64_t flip = 0;                 // amplitude-index positions whose X is left to the store
+  uint32_t absorbed = 0;             // X items of the input that are not in `seg`
+};
+void tile_absorb_x(const std::vector<const TileItem*>& seg, TileAbsorbedX* out);
+// absorb, build the segment's plan from the reduced list (same `high`: the schedule's choice stands) and put the flip, in tile-index
+// bits, into the pass table
+template <typename T>
+int build_tile_segment_absorbed(uint32_t n, const std::vector<const TileItem*>& seg, std::vector<uint32_t> high, TileSegmentPlan<T>* out,
+                                int order_rule, TileAbsorbedX* ab);
+
 // One step of a tiled schedule: a segment of >= 2 gates applied in one sweep, or a single op applied by
 // its own kernel (not tileable, or alone — a lone gate's own kernel touches only what can change).
 struct TileStep {

@@ -607,6 +607,102 @@ template void tile_merge_diag_runs<double>(const TileSegmentPlan<double>&, TileI
 template void tile_merge_diag_runs<float>(const TileSegmentPlan<float>&, TileInterpPlan<float>*, uint32_t);
 
 // ---------------------------------------------------------------------------------------
+// Uncontrolled X gates absorbed (qip_tile.h TileAbsorbedX; interpreter launches only).  X moves amplitudes and rounds nothing, so
+// with P = the set of positions whose X is still pending, the state the kernel holds is the circuit's state with the bits of P
+// flipped, and every later item is conjugated by those flips:
+//   * X on t, no control: toggles t in P and leaves the list;
+//   * a dense 1-qubit gate M on t in P, no control: M.X — columns swapped, the `nz` bits with them — and t leaves P.  Each output is
+//     the same two products as X followed by M, added in the other order: bit-equal.  M.X = 1 (M was a second X in disguise: never
+//     here, X toggles) leaves the list too;
+//   * a diagonal 1-qubit gate on t in P with no control in P: its two entries swapped, t stays pending;
+//   * anything else that touches a pending bit (a control on it, a controlled dense gate, swaps, dense 2- / 3-qubit items): the
+//     X items of those bits come back in front of it, as they were.
+// What is pending at the end is the sweep's flip.  Exactness under tile = 1's ordering rule: the rewritten list in its own order is
+// bit-equal to the segment in its order, and its items commute exactly where the originals did.
+// ---------------------------------------------------------------------------------------
+static bool tile_item_is_plain_x(const TileItem& it) {
+  return it.kind == 0 && it.cpos.empty() && it.nz == 6u && it.m[2] == 1 && it.m[3] == 0 && it.m[4] == 1 && it.m[5] == 0;
+}
+void tile_absorb_x(const std::vector<const TileItem*>& seg, TileAbsorbedX* out) {
+  out->seg.clear();
+  out->owned.clear();
+  uint64_t P = 0;
+  const TileItem* x_of[64] = {nullptr};  // the X item that set the bit: what comes back when the bit is needed
+  for (const TileItem* it : seg) {
+    if (tile_item_is_plain_x(*it)) {
+      P ^= 1ull << it->t0;
+      x_of[it->t0] = it;
+      continue;
+    }
+    const uint64_t touched = (it->nd_mask | it->d_mask) & P;
+    if (!touched) {
+      out->seg.push_back(it);
+      continue;
+    }
+    if (it->kind == 0 && it->cpos.empty()) {  // (touched = its target)
+      TileItem r = *it;
+      std::swap(r.m[0], r.m[2]);
+      std::swap(r.m[1], r.m[3]);
+      std::swap(r.m[4], r.m[6]);
+      std::swap(r.m[5], r.m[7]);
+      r.nz = ((it->nz & 5u) << 1) | ((it->nz & 10u) >> 1);
+      P &= ~touched;
+      if (r.nz == 9u && r.m[0] == 1 && r.m[1] == 0 && r.m[6] == 1 && r.m[7] == 0) continue;
+      out->owned.push_back(r);
+      out->seg.push_back(&out->owned.back());
+      continue;
+    }
+    if (it->kind == 1 && touched == (1ull << it->t0)) {
+      TileItem r = *it;
+      std::swap(r.m[0], r.m[2]);
+      std::swap(r.m[1], r.m[3]);
+      out->owned.push_back(r);
+      out->seg.push_back(&out->owned.back());
+      continue;
+    }
+    for (uint32_t t = 0; t < 64; ++t)
+      if ((touched >> t) & 1ull) out->seg.push_back(x_of[t]);
+    P &= ~touched;
+    out->seg.push_back(it);
+  }
+  out->flip = P;
+  out->absorbed = (uint32_t)(seg.size() - out->seg.size());
+}
+
+template <typename T>
+int build_tile_segment_absorbed(uint32_t n, const std::vector<const TileItem*>& seg, std::vector<uint32_t> high, TileSegmentPlan<T>* out,
+                                int order_rule, TileAbsorbedX* ab) {
+  tile_absorb_x(seg, ab);
+  QCHK(build_tile_segment<T>(n, true, ab->seg, high, out, order_rule));
+  if (ab->absorbed != 0 || !ab->owned.empty()) {
+    // A pass is a round trip of the tile through LDS, worth more than a few X items: an X that came back in front of a control sits
+    // later than it did, and the ordering heuristics of build_tile_segment are not monotone in the list, so the rewritten list can
+    // — rarely — need more passes than the segment as it was.  Then the segment runs as it was.
+    TileSegmentPlan<T> plain;
+    QCHK(build_tile_segment<T>(n, true, seg, high, &plain, order_rule));
+    if (out->pd.npasses > plain.pd.npasses) {
+      *out = std::move(plain);
+      ab->seg = seg;
+      ab->owned.clear();
+      ab->flip = 0;
+      ab->absorbed = 0;
+    }
+  }
+  if (ab->seg.empty()) out->pd.npasses = 0;  // nothing but the flip: a load and a permuted store, no trip of the tile through registers
+  uint32_t flip = 0;
+  for (uint32_t p = 0; p < 64; ++p) {
+    if (!((ab->flip >> p) & 1ull)) continue;
+    const auto f = std::find(out->high.begin(), out->high.end(), p);
+    if (!tile_is_low(p, out->p5) && f == out->high.end()) return fail(QIP_ERR_INVALID, "internal: X target %u outside its tile", p);
+    flip |= 1u << (tile_is_low(p, out->p5) ? tile_low_bit(p) : (uint32_t)kTileLow + (uint32_t)(f - out->high.begin()));
+  }
+  out->pd.flip = flip;
+  return QIP_OK;
+}
+template int build_tile_segment_absorbed<double>(uint32_t, const std::vector<const TileItem*>&, std::vector<uint32_t>, TileSegmentPlan<double>*, int, TileAbsorbedX*);
+template int build_tile_segment_absorbed<float>(uint32_t, const std::vector<const TileItem*>&, std::vector<uint32_t>, TileSegmentPlan<float>*, int, TileAbsorbedX*);
+
+// ---------------------------------------------------------------------------------------
 // Wide tiles (r4): the plan of one segment for the register-resident 13-bit tile (qip_tile.h WidePlan).  Tile bits 0..5 = the
 // rows (positions 0..4 and p5), 6..12 = the seven high positions.  At load / store time the thread id fills tile bits 0..7
 // (rows, then the two wave positions) and a lane's 32 accesses walk tile bits 8..12: that is arrangement 0, and gates on
@@ -1476,6 +1572,70 @@ static int tile_plan_json(int dtype, uint32_t n, const qip_op* ops, uint64_t cou
     }
     js += "]";
   }
+  // one segment plan: the tile's positions, the order, the passes, the gate descriptors and matrices (+ the interpreter's runs)
+  auto emit_segment = [&](const TileSegmentPlan<T>& plan, bool with_interp) {
+    js += ",\"low\":[0,1,2,3,4," + std::to_string(plan.p5) + "],\"high\":[";
+    for (size_t k = 0; k < plan.high.size(); ++k) js += (k ? "," : "") + std::to_string(plan.high[k]);
+    js += "],\"order\":[";
+    for (size_t k = 0; k < plan.order.size(); ++k) js += (k ? "," : "") + std::to_string(plan.order[k]);
+    js += "],\"passes\":[";
+    for (uint32_t pi = 0; pi < plan.pd.npasses; ++pi) {
+      const TilePass& ps = plan.pd.pass[pi];
+      if (pi) js += ",";
+      js += "{\"first\":" + std::to_string(ps.first) + ",\"count\":" + std::to_string(ps.count) + ",\"pb\":[" +
+            std::to_string(ps.pb[0]) + "," + std::to_string(ps.pb[1]) + "," + std::to_string(ps.pb[2]) +
+            "],\"lanepos\":[";
+      for (int k = 0; k < kTileLaneBits; ++k) js += (k ? "," : "") + std::to_string((unsigned)((ps.lanepos >> (4 * k)) & 15ull));
+      js += "]}";
+    }
+    js += "],\"gates\":[";
+    for (size_t gi = 0; gi < plan.gates.size(); ++gi) {
+      const TileGate<T>& g = plan.gates[gi];
+      if (gi) js += ",";
+      js += "{\"kind\":" + std::to_string(g.kind) + ",\"op\":" + std::to_string(g.op) + ",\"b0\":" +
+            std::to_string(g.b0) + ",\"b1\":" + std::to_string(g.b1) + ",\"cmask\":" + std::to_string(g.cmask) +
+            ",\"cm_reg\":" + std::to_string(g.cm_reg) + ",\"cm_lane\":" + std::to_string(g.cm_lane) +
+            ",\"omask\":" + std::to_string(g.omask) + ",\"tpos_out\":" + std::to_string(g.tpos_out) +
+            ",\"nz\":" + std::to_string(g.nz) + ",\"m\":[";
+      for (int e = 0; e < 4; ++e)
+        js += std::string(e ? "," : "") + "[" + num((double)g.m[e].x) + "," + num((double)g.m[e].y) + "]";
+      js += "]}";
+    }
+    js += "],\"mats\":[";
+    for (size_t e = 0; e < plan.mats.size(); ++e)
+      js += std::string(e ? "," : "") + "[" + num((double)plan.mats[e].x) + "," + num((double)plan.mats[e].y) + "]";
+    js += "]";
+    if (with_interp) {  // r5: what the interpreter kernel is handed instead — runs of diagonal gates as TileDiagItem steps
+      TileInterpPlan<T> ip;
+      tile_merge_diag_runs<T>(plan, &ip);
+      js += ",\"interp\":{\"runs\":" + std::to_string(ip.runs) + ",\"gates_in_runs\":" + std::to_string(ip.gates_in_runs) + ",\"passes\":[";
+      for (uint32_t pi = 0; pi < ip.pd.npasses; ++pi)
+        js += std::string(pi ? "," : "") + "[" + std::to_string(ip.pd.pass[pi].first) + "," + std::to_string(ip.pd.pass[pi].count) + "]";
+      js += "],\"gates\":[";
+      for (size_t gi = 0; gi < ip.gates.size(); ++gi) {
+        const TileGate<T>& g = ip.gates[gi];
+        if (gi) js += ",";
+        if (g.op == (uint32_t)TOP_DIAG_RUN) {
+          js += "{\"run\":[" + std::to_string(g.nz) + "," + std::to_string(g.b1) + "]}";
+        } else {
+          size_t src = 0;  // an unchanged gate: its index in the plan's list
+          for (; src < plan.gates.size(); ++src)
+            if (!memcmp(&plan.gates[src], &g, sizeof g)) break;
+          js += "{\"gate\":" + std::to_string(src) + "}";
+        }
+      }
+      js += "],\"items\":[";
+      for (size_t k = 0; k < ip.items.size(); ++k) {
+        const TileDiagItem<T>& it = ip.items[k];
+        js += std::string(k ? "," : "") + "{\"f0\":[" + num((double)it.f0.x) + "," + num((double)it.f0.y) + "],\"f1\":[" + num((double)it.f1.x) + "," +
+              num((double)it.f1.y) + "],\"lane\":[" + std::to_string(it.lane_mask) + "," + std::to_string(it.lane_val) + "],\"reg\":[" +
+              std::to_string(it.reg_pack & 0xffffu) + "," + std::to_string(it.reg_pack >> 16) + "],\"out\":[" + std::to_string(it.omask) + "," +
+              std::to_string(it.oval) + "],\"sel\":" + std::to_string((it.emask_sel >> 24) ? 1u << ((it.emask_sel >> 24) - 1u) : 0u) +
+              ",\"emask\":" + std::to_string(it.emask_sel & 0xffu) + "}";
+      }
+      js += "]}";
+    }
+  };
   js += ",\"steps\":[";
   for (size_t si = 0; si < steps.size(); ++si) {
     const TileStep& st = steps[si];
@@ -1531,66 +1691,21 @@ static int tile_plan_json(int dtype, uint32_t n, const qip_op* ops, uint64_t cou
       for (uint64_t i : st.ops) seg.push_back(&items[i]);
       TileSegmentPlan<T> plan;
       QCHK(build_tile_segment<T>(n, true, seg, st.high, &plan, mode & 3));
-      js += ",\"low\":[0,1,2,3,4," + std::to_string(plan.p5) + "],\"high\":[";
-      for (size_t k = 0; k < plan.high.size(); ++k) js += (k ? "," : "") + std::to_string(plan.high[k]);
-      js += "],\"order\":[";
-      for (size_t k = 0; k < plan.order.size(); ++k) js += (k ? "," : "") + std::to_string(plan.order[k]);
-      js += "],\"passes\":[";
-      for (uint32_t pi = 0; pi < plan.pd.npasses; ++pi) {
-        const TilePass& ps = plan.pd.pass[pi];
-        if (pi) js += ",";
-        js += "{\"first\":" + std::to_string(ps.first) + ",\"count\":" + std::to_string(ps.count) + ",\"pb\":[" +
-              std::to_string(ps.pb[0]) + "," + std::to_string(ps.pb[1]) + "," + std::to_string(ps.pb[2]) +
-              "],\"lanepos\":[";
-        for (int k = 0; k < kTileLaneBits; ++k) js += (k ? "," : "") + std::to_string((unsigned)((ps.lanepos >> (4 * k)) & 15ull));
-        js += "]}";
-      }
-      js += "],\"gates\":[";
-      for (size_t gi = 0; gi < plan.gates.size(); ++gi) {
-        const TileGate<T>& g = plan.gates[gi];
-        if (gi) js += ",";
-        js += "{\"kind\":" + std::to_string(g.kind) + ",\"op\":" + std::to_string(g.op) + ",\"b0\":" +
-              std::to_string(g.b0) + ",\"b1\":" + std::to_string(g.b1) + ",\"cmask\":" + std::to_string(g.cmask) +
-              ",\"cm_reg\":" + std::to_string(g.cm_reg) + ",\"cm_lane\":" + std::to_string(g.cm_lane) +
-              ",\"omask\":" + std::to_string(g.omask) + ",\"tpos_out\":" + std::to_string(g.tpos_out) +
-              ",\"nz\":" + std::to_string(g.nz) + ",\"m\":[";
-        for (int e = 0; e < 4; ++e)
-          js += std::string(e ? "," : "") + "[" + num((double)g.m[e].x) + "," + num((double)g.m[e].y) + "]";
-        js += "]}";
-      }
-      js += "],\"mats\":[";
-      for (size_t e = 0; e < plan.mats.size(); ++e)
-        js += std::string(e ? "," : "") + "[" + num((double)plan.mats[e].x) + "," + num((double)plan.mats[e].y) + "]";
-      js += "]";
-      if (mode & 1024) {  // r5: what the interpreter kernel is handed instead — runs of diagonal gates as TileDiagItem steps
-        TileInterpPlan<T> ip;
-        tile_merge_diag_runs<T>(plan, &ip);
-        js += ",\"interp\":{\"runs\":" + std::to_string(ip.runs) + ",\"gates_in_runs\":" + std::to_string(ip.gates_in_runs) + ",\"passes\":[";
-        for (uint32_t pi = 0; pi < ip.pd.npasses; ++pi)
-          js += std::string(pi ? "," : "") + "[" + std::to_string(ip.pd.pass[pi].first) + "," + std::to_string(ip.pd.pass[pi].count) + "]";
-        js += "],\"gates\":[";
-        for (size_t gi = 0; gi < ip.gates.size(); ++gi) {
-          const TileGate<T>& g = ip.gates[gi];
-          if (gi) js += ",";
-          if (g.op == (uint32_t)TOP_DIAG_RUN) {
-            js += "{\"run\":[" + std::to_string(g.nz) + "," + std::to_string(g.b1) + "]}";
-          } else {
-            size_t src = 0;  // an unchanged gate: its index in the plan's list
-            for (; src < plan.gates.size(); ++src)
-              if (!memcmp(&plan.gates[src], &g, sizeof g)) break;
-            js += "{\"gate\":" + std::to_string(src) + "}";
+      emit_segment(plan, (mode & 1024) != 0);
+      if (mode & 4096) {  // what the interpreter kernel is really handed: the list with its X gates absorbed, that list's passes and runs, the flip
+        TileSegmentPlan<T> ap;
+        TileAbsorbedX ab;
+        QCHK(build_tile_segment_absorbed<T>(n, seg, st.high, &ap, mode & 3, &ab));
+        js += ",\"absorb\":{\"flip\":" + std::to_string(ap.pd.flip) + ",\"flip_pos\":[";
+        bool any = false;
+        for (uint32_t p = 0; p < 64; ++p)
+          if ((ab.flip >> p) & 1ull) {
+            js += (any ? "," : "") + std::to_string(p);
+            any = true;
           }
-        }
-        js += "],\"items\":[";
-        for (size_t k = 0; k < ip.items.size(); ++k) {
-          const TileDiagItem<T>& it = ip.items[k];
-          js += std::string(k ? "," : "") + "{\"f0\":[" + num((double)it.f0.x) + "," + num((double)it.f0.y) + "],\"f1\":[" + num((double)it.f1.x) + "," +
-                num((double)it.f1.y) + "],\"lane\":[" + std::to_string(it.lane_mask) + "," + std::to_string(it.lane_val) + "],\"reg\":[" +
-                std::to_string(it.reg_pack & 0xffffu) + "," + std::to_string(it.reg_pack >> 16) + "],\"out\":[" + std::to_string(it.omask) + "," +
-                std::to_string(it.oval) + "],\"sel\":" + std::to_string((it.emask_sel >> 24) ? 1u << ((it.emask_sel >> 24) - 1u) : 0u) +
-                ",\"emask\":" + std::to_string(it.emask_sel & 0xffu) + "}";
-        }
-        js += "]}";
+        js += "],\"dropped\":" + std::to_string(ab.absorbed);
+        emit_segment(ap, true);
+        js += "}";
       }
     }
     js += "}";

@@ -316,9 +316,15 @@ def debug_sparse_tile(n: int, op, dtype: int = _ffi.QIP_C64) -> dict:
     return json.loads(txt.decode() if isinstance(txt, bytes) else txt)
 
 
+TILE_PLAN_INTERP, TILE_PLAN_ABSORB_X = 1024, 4096  # mode bits of debug_tile_plan
+
+
 def debug_tile_plan(n: int, ops, mode: int = 1, dtype: int = _ffi.QIP_C64) -> dict:
     """Host-only test hook (qip_hip_debug_tile_plan): the tile schedule plus every segment's passes and gate
-    descriptors as shipped to the kernel, parsed from JSON."""
+    descriptors as shipped to the kernel, parsed from JSON.  `mode`: the schedule mode, plus TILE_PLAN_INTERP (every
+    multi-gate step gains "interp": its runs of diagonal gates as the interpreter kernel takes them) and TILE_PLAN_ABSORB_X
+    (every multi-gate step gains "absorb": the step as the interpreter kernel is really handed it, uncontrolled X gates
+    absorbed into their neighbours and into "flip", the tile-index bits its store flips)."""
     import json
 
     cops = [op.to_c(dtype) for op in ops]

@@ -1,7 +1,7 @@
 """Per-sweep table of the headline's default-path tile sweeps from a rocprofv3 kernel trace of
 `bench.py --headline-only --steps K --warmup W` (K + W steps of 15 sweeps each, after the product-state preparation).
 
-    python tools/sweep_table.py <..._kernel_trace.csv> [steps]
+    python tools/sweep_table.py <..._kernel_trace.csv> [steps] [parent]
 
 Host-only: the gate list of each sweep comes from the mode-1 tile plan (qip_hip_debug_tile_plan), the times from the
 last `steps` x (sweeps per step) k_tile_passes dispatches of the trace; prints a markdown table."""
@@ -19,9 +19,11 @@ N, GATES = 30, 256
 HBM = 8.0e12
 
 
-def main(path, steps):
+def main(path, steps, parent=False):
     ops = circuits.c2_random_circuit(N, GATES, seed=28, single_only=True)
-    plan = [s for s in debug_tile_plan(N, ops, 1)["steps"] if len(s["ops"]) >= 2]
+    # the lists the interpreter is handed: uncontrolled X gates absorbed (mode bit 4096); `parent`: a trace of a build from before
+    # that rewrite, the plan's own lists
+    plan = [s if parent else s["absorb"] for s in debug_tile_plan(N, ops, 1 | (0 if parent else 4096))["steps"] if len(s["ops"]) >= 2]
     rows = [r for r in csv.DictReader(open(path)) if "k_tile_passes" in r["Kernel_Name"]]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     per = len(plan)
@@ -46,4 +48,4 @@ def main(path, steps):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1], int(sys.argv[2]) if len(sys.argv) > 2 else 4)
+    main(sys.argv[1], int(sys.argv[2]) if len(sys.argv) > 2 else 4, parent=len(sys.argv) > 3 and sys.argv[3] == "parent")
