@@ -2,7 +2,8 @@
 //! is built for — the reference functions are generic over `P` (`qip-iterators/src/matrix_ops.rs:38-59,98-152`; its unit
 //! tests run them on `i32`, its benches on `f64`).  Same argument order as the reference; host slices (the call uploads,
 //! runs the HIP kernels, downloads) or device pointers ([`apply_op_device`]).  Results are bit-equal to the CPU fold for
-//! real and integer `P` (one lane folds one row in the reference's order; integers wrap as in a release build).
+//! real and integer `P`, and on device slices for complex `P` too (every row is folded in the reference's order; integers
+//! wrap as in a release build).
 //!
 //! Status: **uncompiled**, like the rest of this crate (see `lib.rs`).
 use crate::state::{check, HipError};
@@ -142,7 +143,8 @@ pub fn apply_op_row<E: HipElement + Default>(
 }
 
 /// The same on device slices: `d_in` / `d_out` are device pointers to `in_len` / `out_len` elements on `device`, `stream`
-/// a `hipStream_t` (null = the null stream).  A dense op on <= 4 qubits or a `Swap` is one asynchronous launch.
+/// a `hipStream_t` (null = the null stream).  A dense op on <= 4 qubits (complex `E`: <= 3) or a `Swap`, <= 4 indices with
+/// the controls, is one asynchronous launch for every `E`, complex included; anything wider synchronises the stream.
 ///
 /// # Safety
 /// The pointers must be valid device allocations of the stated lengths that do not alias.

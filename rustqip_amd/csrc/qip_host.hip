@@ -484,8 +484,158 @@ static int apply_op_real_device(uint32_t n, const qip_op* op, const R* d_in, uin
   return rc;
 }
 
-// complex P on device slices: the literal kernel of the state path (k_gather_generic) through a handle that adopts the caller's
-// stream and owns only the payload arena
+// ---- complex P: the same two kernels on Complex<f64> / Complex<f32> slices ------------------------------------------------------
+// A dense op on k <= 3 qubits (64 entries: 1 KiB of Complex<f64>; a 4-qubit table is 4 KiB and does not fit the kernel-argument
+// segment) or a Swap, k_all <= 4 indices with the controls: the table travels in the kernel arguments, the call only launches.
+template <typename T> struct CplxTab {
+  amp_t<T> v[64];
+};
+
+// the literal fold of k_gather_generic, one output row per lane, any window; only the table's home differs
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_gather_cplx(const amp_t<T>* __restrict__ in, amp_t<T>* __restrict__ out, GatherDesc d,
+                                                        CplxTab<T> tab) {
+  using A = amp_t<T>;
+  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+  for (uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x; r < d.out_len; r += stride) {
+    const uint64_t row = d.out_off + r;
+    const uint64_t matrow = g_full_to_sub(d, row);
+    A acc = czero<A>();
+    A one;
+    one.x = 1;
+    one.y = 0;
+    const uint64_t thr = (1ull << (d.n_control + d.n_op)) - (1ull << d.n_op);  // (0 without controls)
+    if (matrow < thr) {  // outside the control subspace
+      acc = cadd(acc, g_term<T>(d, row, matrow, one, in));
+    } else if (d.inner_kind == 0) {  // MATRIX
+      const uint64_t side = 1ull << d.n_op;
+      for (uint64_t c = 0; c < side; ++c) {
+        const A v = tab.v[(matrow - thr) * side + c];
+        if (!(v.x == (T)0 && v.y == (T)0)) acc = cadd(acc, g_term<T>(d, row, c + thr, v, in));
+      }
+    } else {  // SWAP
+      const uint32_t half_n = d.n_op >> 1;
+      const uint64_t irow = matrow - thr, lower_mask = ~(~0ull << half_n);
+      const uint64_t col = ((irow & lower_mask) << half_n) + (irow >> half_n);
+      acc = cadd(acc, g_term<T>(d, row, col + thr, one, in));
+    }
+    out[r] = d.accumulate ? cadd(out[r], acc) : acc;
+  }
+}
+
+// k_real_groups for a complex element E: one amplitude (amp_t<T>), or f32x4 = two adjacent Complex<f32> (no index bit at
+// position 0, d.off / ins in units of pairs).  The lane reads its 2^K elements once and folds every row as the literal kernel
+// does: acc = 0; acc = cadd(acc, cmul(m[row][c], x[c])) for c ascending, an entry skipped only when both parts are zero (a scalar
+// branch); a row outside the control subspace or of a Swap is 0 + (1 + 0i) * x[col].  Bit-equal to k_gather_generic.
+template <typename T, typename E, int K, int NC, bool SWAP, bool NT>
+__global__ __launch_bounds__(kBlock) void k_cplx_groups(const E* __restrict__ in, E* __restrict__ out, Ins ins, RealGroupDesc d,
+                                                        CplxTab<T> tab) {
+  using A = amp_t<T>;
+  constexpr int M = 1 << K, KOP = K - NC, SIDE = 1 << KOP, THR = M - SIDE;
+  const uint64_t w = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (w >= d.nitems) return;
+  const uint64_t base = insert_bits<K>(w, ins);
+  A one;
+  one.x = 1;
+  one.y = 0;
+  E x[M];
+#pragma unroll
+  for (int m = 0; m < M; ++m) x[m] = ldg<NT>(in + (base | d.off[m]));
+#pragma unroll
+  for (int m = 0; m < M; ++m) {
+    E acc = czero<E>();
+    if (m < THR) {
+      acc = cadd(acc, cmul(one, x[m]));
+    } else if constexpr (SWAP) {
+      constexpr int HALF = KOP >> 1;
+      const int irow = m - THR;
+      const int col = ((irow & ((1 << HALF) - 1)) << HALF) + (irow >> HALF);
+      acc = cadd(acc, cmul(one, x[col + THR]));
+    } else {
+#pragma unroll
+      for (int c = 0; c < SIDE; ++c) {
+        const A v = tab.v[(m - THR) * SIDE + c];
+        if (!(v.x == (T)0 && v.y == (T)0)) acc = cadd(acc, cmul(v, x[c + THR]));
+      }
+    }
+    const uint64_t at = base | d.off[m];
+    stg<NT>(out + at, d.accumulate ? cadd(ldg<NT>(out + at), acc) : acc);
+  }
+}
+
+template <typename T, typename E, int K, bool NT>
+static int launch_cplx_groups_k(const FlatOp& f, const E* d_in, E* d_out, const Ins& ins, const RealGroupDesc& d, const CplxTab<T>& tab,
+                                hipStream_t stream) {
+  const dim3 grid((unsigned)((d.nitems + kBlock - 1) / kBlock)), block(kBlock);
+  const bool swap = f.inner->kind == QIP_OP_SWAP;
+#define CG(NC, SW)                                                                                                       \
+  hipLaunchKernelGGL((k_cplx_groups<T, E, K, NC, SW, NT>), grid, block, 0, stream, d_in, d_out, ins, d, tab)
+  const int nc = (int)f.n_control;  // (the caller admits a dense op on <= 3 qubits: K - nc <= 3)
+  if (swap) {
+    if constexpr (K == 2) { CG(0, true); }
+    else if constexpr (K == 3) { CG(1, true); }
+    else if constexpr (K == 4) { if (nc == 0) CG(0, true); else CG(2, true); }
+  } else {
+    if constexpr (K == 1) { CG(0, false); }
+    else if constexpr (K == 2) { if (nc == 0) CG(0, false); else CG(1, false); }
+    else if constexpr (K == 3) { if (nc == 0) CG(0, false); else if (nc == 1) CG(1, false); else CG(2, false); }
+    else { if (nc == 1) CG(1, false); else if (nc == 2) CG(2, false); else CG(3, false); }
+  }
+#undef CG
+  HIPCHK(hipGetLastError());
+  return QIP_OK;
+}
+
+// the whole vector, distinct indices, K = k_all <= 4 < n (the caller checked the op's kind and size)
+template <typename T>
+static int launch_cplx_groups(uint32_t n, const FlatOp& f, const amp_t<T>* d_in, amp_t<T>* d_out, const CplxTab<T>& tab, int accumulate,
+                              hipStream_t stream) {
+  using A = amp_t<T>;
+  const uint32_t K = f.k_all;
+  uint32_t lowest = 64;
+  std::vector<uint32_t> pos(K);
+  for (uint32_t j = 0; j < K; ++j) {
+    pos[j] = (uint32_t)(n - 1 - f.outer->indices[j]);
+    lowest = std::min(lowest, pos[j]);
+  }
+  // Complex<f32>: pairs of amplitudes (f32x4) when no index sits at position 0 and both slices start on a 16-byte boundary
+  const bool pairs = sizeof(A) == 8 && lowest >= 1 && n >= K + 1 && (uintptr_t)d_in % 16 == 0 && (uintptr_t)d_out % 16 == 0;
+  const uint32_t lv = pairs ? 1u : 0u;
+  RealGroupDesc d;
+  memset(&d, 0, sizeof d);
+  d.nitems = 1ull << (n - K - lv);
+  d.accumulate = accumulate;
+  for (uint32_t m = 0; m < (1u << K); ++m)
+    for (uint32_t j = 0; j < K; ++j) d.off[m] |= (uint64_t)((m >> (K - 1 - j)) & 1u) << (pos[j] - lv);
+  std::vector<uint32_t> opened(K);
+  for (uint32_t j = 0; j < K; ++j) opened[j] = pos[j] - lv;
+  const Ins ins = make_ins(opened, 0);
+  // non-temporal accesses under the rule of the real path: a vector of at least 64 MiB, 16-byte elements, waves that cover
+  // whole 128-byte lines (no index bit within the low three element positions)
+  const bool nt = (sizeof(A) == 16 || pairs) && (sizeof(A) << n) >= (64ull << 20) && lowest - lv >= 3;
+#define CK(KK)                                                                                                               \
+  if constexpr (sizeof(A) == 8) {                                                                                           \
+    if (pairs)                                                                                                               \
+      return nt ? launch_cplx_groups_k<T, f32x4, KK, true>(f, (const f32x4*)d_in, (f32x4*)d_out, ins, d, tab, stream)        \
+                : launch_cplx_groups_k<T, f32x4, KK, false>(f, (const f32x4*)d_in, (f32x4*)d_out, ins, d, tab, stream);      \
+    return launch_cplx_groups_k<T, A, KK, false>(f, d_in, d_out, ins, d, tab, stream);                                       \
+  } else {                                                                                                                   \
+    return nt ? launch_cplx_groups_k<T, A, KK, true>(f, d_in, d_out, ins, d, tab, stream)                                    \
+              : launch_cplx_groups_k<T, A, KK, false>(f, d_in, d_out, ins, d, tab, stream);                                  \
+  }
+  switch (K) {
+    case 1: CK(1)
+    case 2: CK(2)
+    case 3: CK(3)
+    default: CK(4)
+  }
+#undef CK
+}
+
+// complex P on device slices.  A dense op on <= 3 qubits or a Swap with k_all <= 4 indices: ONE launch on the caller's stream and
+// nothing else (no handle, no allocation, no copy, no synchronisation) — k_cplx_groups for the whole vector, k_gather_cplx for
+// windows.  Everything else (SparseMatrix, wider ops, option force_generic): the literal kernel of the state path
+// (k_gather_generic) through a handle that adopts the caller's stream and owns only the payload arena; that route synchronises.
 template <typename T>
 static int apply_op_complex_device(int dtype, int device, hipStream_t stream, uint32_t n, const qip_op* op, const void* d_in,
                                    uint64_t in_len, void* d_out, uint64_t out_len, uint64_t in_off, uint64_t out_off,
@@ -493,6 +643,31 @@ static int apply_op_complex_device(int dtype, int device, hipStream_t stream, ui
   FlatOp f;
   QCHK(flatten_op(n, op, false, &f));
   if (out_len == 0) return QIP_OK;
+  const bool swap = f.inner->kind == QIP_OP_SWAP && !(f.n_op & 1u);
+  if (!g_force_generic && f.k_all <= 4 && (swap || (f.inner->kind == QIP_OP_MATRIX && f.n_op <= 3))) {
+    CplxTab<T> tab;
+    memset(&tab, 0, sizeof tab);
+    if (!swap) memcpy(tab.v, f.inner->dense, sizeof(amp_t<T>) << (2 * f.n_op));
+    if (in_off == 0 && out_off == 0 && in_len == (1ull << n) && out_len == in_len && f.distinct && f.k_all < n)
+      return launch_cplx_groups<T>(n, f, (const amp_t<T>*)d_in, (amp_t<T>*)d_out, tab, accumulate, stream);
+    GatherDesc d;
+    memset(&d, 0, sizeof d);
+    d.n = n;
+    d.k_all = f.k_all;
+    d.n_control = f.n_control;
+    d.n_op = f.n_op;
+    d.inner_kind = f.inner->kind;
+    d.accumulate = accumulate;
+    d.in_len = in_len;
+    d.out_len = out_len;
+    d.in_off = in_off;
+    d.out_off = out_off;
+    for (uint32_t j = 0; j < f.k_all; ++j) d.pos[j] = (uint32_t)(n - 1 - f.outer->indices[j]);
+    hipLaunchKernelGGL((k_gather_cplx<T>), dim3(grid_stride(out_len)), dim3(kBlock), 0, stream, (const amp_t<T>*)d_in, (amp_t<T>*)d_out, d,
+                       tab);
+    HIPCHK(hipGetLastError());
+    return QIP_OK;
+  }
   qip_hip_state* s = nullptr;
   QCHK(qip_hip_state_wrap(n, dtype, device, d_out, nullptr, (void*)stream, &s));
   int rc = launch_gather<T>(s, f, (const amp_t<T>*)d_in, in_len, (amp_t<T>*)d_out, out_len, in_off, out_off, accumulate);

@@ -126,7 +126,9 @@ def apply_op_device(n: int, op: MatrixOp, input, output, input_offset: int = 0, 
                     accumulate: bool = True, stream: int = 0) -> None:
     """apply_op (accumulate) / apply_op_overwrite on DEVICE slices for any `P` (qip_hip_apply_op_device): `input` / `output`
     are DeviceSlice objects or contiguous 1-D torch tensors on one GPU, `stream` a raw hipStream_t (0 = null stream).  Nothing
-    is copied to the host; with a dense op on k <= 4 qubits or a Swap the call only launches.  `op` may be a MatrixOp or the
+    is copied to the host; with a dense op on k <= 4 qubits (complex `P`: k <= 3) or a Swap, at most 4 indices with the controls,
+    the call only launches on `stream` for every `P` — it can be recorded into a hipGraph — and over the whole vector it reads
+    each input once; SparseMatrix and wider ops synchronise the stream.  `op` may be a MatrixOp or the
     descriptor `op.to_c(dtype)` built once (the reference's benches build their op once, outside the timed loop)."""
     i, o = _as_slice(input), _as_slice(output)
     if i.dtype != o.dtype or i.device != o.device:
