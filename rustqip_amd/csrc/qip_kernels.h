@@ -1504,6 +1504,7 @@ constexpr int kTileMaxGates = 256;
 // such a bit is constant for the whole block, so it is tested once against the block's base index
 // (`omask` / `tpos_out`, amplitude-index space) instead of per element (`cmask` / `b0`, tile-index space).
 constexpr uint32_t kTileOutside = 0xffffffffu;
+constexpr uint32_t kTileSignRows = 4u, kTileSignNeg0 = 8u, kTileSignNeg1 = 16u;  // TileGate::b1 of a dense 1-qubit gate, see there
 template <typename T> struct TileGate {
   uint32_t kind;      // 0 = dense 1-qubit (pair update), 1 = diagonal 1-qubit (factor by target bit), 2 = bit swap,
                       // 3 = dense 2-qubit (b0 = bit of the sub-index MSB, b1 = LSB; nz = index of its 4x4 matrix),
@@ -1515,6 +1516,13 @@ template <typename T> struct TileGate {
                       //   bit 1: the gate is X ([0,1;1,0])   -> the pair is exchanged, no arithmetic
                       // both give IEEE-equal results for finite amplitudes (x*1 == x, a - 0*b == a); inside a
                       // tile sweep VALU issue, not HBM, is the limit, so instructions matter here
+                      //   bit 2 (kTileSignRows): row 1 is row 0 up to one sign per column, no entry zero (H, H.X,
+                      //          Ry(pi/2)) -> with real entries row 0's products serve both rows, half the multiplies
+                      //          (pass_dense_signs; complex entries: marked, and run by the generic body)
+                      //   bit 3 (kTileSignNeg0): m[2] == -m[0], else m[2] == m[0]      } compared bit by bit: (-m)*x
+                      //   bit 4 (kTileSignNeg1): m[3] == -m[1], else m[3] == m[1]      } is -(m*x) in every bit
+                      // bits 2..4 are set only in the lists of the interpreter's multi-gate sweeps (tile_mark_sign_rows,
+                      // after tile_absorb_x): plans, their exports and the generated kernels keep b1 & 3
   uint32_t cmask;     // tile-index bits that must all be 1 (controls inside the tile)
   uint32_t nz;        // kind 0: non-zero mask of the 2x2 entries
   uint32_t tpos_out;  // kind 1 with b0 == kTileOutside: amplitude-index position of the target
@@ -1725,6 +1733,10 @@ struct TilePassDesc {
 //     gfx950 inline assembly with "+v" operands (operands copied in and out: 2186 vs 1602 vector instructions
 //     per wave for 20 Hadamards), scalar re[8]/im[8] registers with products-before-sums ordering (1825, and the
 //     X exchange if-converted into selects: 2959 vs 1256);
+//   * a dense gate whose second row is its first up to one sign per column (H, H.X after tile_absorb_x, Ry(pi/2)) multiplies
+//     once for both rows: (-m)*x is -(m*x) in every bit and the negation rides on the add as a source modifier, so a Hadamard is
+//     16 mul + 16 add per lane instead of 32 + 16.  The four sign patterns are four straight-line variants behind scalar branches
+//     (pass_dense_signs): a per-lane sign select would cost the instructions the shared products save;
 //   * wave-uniform conditions stay BRANCHES (QIP_KEEP_BRANCH): if-converted they become speculative arithmetic
 //     blended by v_cndmask — more instructions and ~100 more live registers;
 //   * global addresses are a wave-uniform base plus the lane id.
@@ -1780,6 +1792,52 @@ __device__ __forceinline__ void pass_dense_body(const TileGate<T>& g, amp_t<T> (
   }
 }
 
+// p + q with the signs of a sign-symmetric second row (N0 / N1: the first / second term is negated).  (-p) + q is q - p and
+// (-p) + (-q) is (-p) - q in every bit, and a negated operand is a source modifier of the add: no instruction of its own
+template <bool N0, bool N1, typename T> __device__ __forceinline__ T tile_signed_sum(T p, T q) {
+  if constexpr (N0 && N1) return (-p) - q;
+  else if constexpr (N0) return q - p;
+  else if constexpr (N1) return p - q;
+  else return p + q;
+}
+
+// dense 1-qubit gate of REAL entries on pass bit J whose second row is its first up to one sign per column (TileGate::b1 bits
+// 2..4: m[2] = +-m[0], m[3] = +-m[1], no entry zero), no control on a pass bit.  The products of row 0 serve row 1: (-m)*x is
+// -(m*x) bit for bit, so every output is the sum pass_dense_body forms, from half the multiplies: 16 mul + 16 add per gate and
+// lane instead of 32 + 16.
+// (The complex form — cmul(-m, x) = (yy - xx, (-xy) - yx) from the four products of cmul(m, x), 32 mul + 48 add instead of 64 + 48
+// — is not here: with its eight variants beside these the Complex<f64> kernel spilled 36 - 64 VGPRs under the five-blocks-per-CU
+// bound, whether its products were formed all at once or a column at a time.  Complex gates of this shape carry the bits and
+// take pass_dense_body.)
+template <typename T, int J, bool N0, bool N1, int NE>
+__device__ __forceinline__ void pass_dense_signs_body(const TileGate<T>& g, amp_t<T> (&e)[NE]) {
+  using A = amp_t<T>;
+  const T m0 = g.m[0].x, m1 = g.m[1].x;
+#pragma unroll
+  for (int i = 0; i < NE; ++i) {
+    if ((i >> J) & 1) continue;
+    const int k = i | (1 << J);
+    const A a0 = e[i], a1 = e[k];
+    const T p0x = m0 * a0.x, p0y = m0 * a0.y, p1x = m1 * a1.x, p1y = m1 * a1.y;
+    e[i].x = p0x + p1x;
+    e[i].y = p0y + p1y;
+    e[k].x = tile_signed_sum<N0, N1>(p0x, p1x);
+    e[k].y = tile_signed_sum<N0, N1>(p0y, p1y);
+    __builtin_amdgcn_sched_barrier(0);  // one butterfly at a time, as in pass_dense_body
+  }
+}
+
+// the four sign combinations are wave-uniform: straight-line variants whose add / subtract is fixed at compile time, behind branches
+template <typename T, int J, int NE>
+__device__ __forceinline__ void pass_dense_signs(const TileGate<T>& g, amp_t<T> (&e)[NE]) {
+  switch (g.b1 & (kTileSignNeg0 | kTileSignNeg1)) {
+    case 0u: pass_dense_signs_body<T, J, false, false, NE>(g, e); break;
+    case kTileSignNeg1: pass_dense_signs_body<T, J, false, true, NE>(g, e); break;
+    case kTileSignNeg0: pass_dense_signs_body<T, J, true, false, NE>(g, e); break;
+    default: pass_dense_signs_body<T, J, true, true, NE>(g, e); break;
+  }
+}
+
 template <typename T, int J, int NE>
 __device__ __forceinline__ void pass_dense(const TileGate<T>& g, amp_t<T> (&e)[NE], const uint32_t (&c)[NE], uint32_t cm) {
   using A = amp_t<T>;
@@ -1797,7 +1855,10 @@ __device__ __forceinline__ void pass_dense(const TileGate<T>& g, amp_t<T> (&e)[N
     }
     return;
   }
-  if (cm == 0u && g.nz == 15u) {
+  if (cm == 0u && real && (g.b1 & kTileSignRows) != 0) {  // (the host sets the bit only where all four entries are non-zero)
+    QIP_KEEP_BRANCH();
+    pass_dense_signs<T, J, NE>(g, e);
+  } else if (cm == 0u && g.nz == 15u) {
     if (real) pass_dense_body<T, J, true, false, NE>(g, e, c, cm);
     else pass_dense_body<T, J, false, false, NE>(g, e, c, cm);
   } else {

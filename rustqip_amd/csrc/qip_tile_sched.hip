@@ -1,6 +1,7 @@
 // qip_tile_sched.hip — the host-only half of the LDS-resident tile sweeps: which gates form a segment, the passes of a
 // segment, the qubit relabelling, and the plan export the CPU tests replay.  No kernel is launched from this file.
 #include "qip_tile.h"
+#include <type_traits>
 #include <array>
 
 // ---------------------------------------------------------------------------------------
@@ -669,6 +670,35 @@ void tile_absorb_x(const std::vector<const TileItem*>& seg, TileAbsorbedX* out) 
   out->absorbed = (uint32_t)(seg.size() - out->seg.size());
 }
 
+// Dense 1-qubit gates whose second row is the first up to one sign per column (TileGate::b1 bits 2..4; H, and H.X where an X was
+// absorbed): k_tile_passes forms both rows from row 0's products (pass_dense_signs).  Marked here, in the list the interpreter
+// kernel is handed and nowhere else: the plans of build_tile_segment, their exports and the sources generated from them do not
+// carry the bits.  The test is on the entries as the kernel multiplies them, bit by bit: an entry equals its partner, or is its
+// negation in BOTH components — (-m)*x is then -(m*x) in every bit of every product; a conjugate or a flip of one component is
+// neither.  A gate of real entries never multiplies by the imaginary parts (b1 bit 0), so only its real parts are compared.
+template <typename T>
+static void tile_mark_sign_rows(std::vector<TileGate<T>>* gates) {
+  using U = typename std::conditional<sizeof(T) == 8, uint64_t, uint32_t>::type;
+  constexpr U kSign = (U)1 << (8 * sizeof(T) - 1);
+  auto bits = [](T v) {
+    U u;
+    memcpy(&u, &v, sizeof u);
+    return u;
+  };
+  for (TileGate<T>& g : *gates) {
+    if (g.kind != 0 || g.nz != 15u || (g.b1 & 2u)) continue;
+    const bool real = (g.b1 & 1u) != 0;
+    uint32_t flags = kTileSignRows;
+    for (int col = 0; col < 2 && flags; ++col) {
+      const amp_t<T> a = g.m[col], b = g.m[2 + col];
+      const U dx = bits(a.x) ^ bits(b.x), dy = real ? dx : bits(a.y) ^ bits(b.y);
+      if (dx == kSign && dy == kSign) flags |= col == 0 ? kTileSignNeg0 : kTileSignNeg1;
+      else if (dx != 0 || dy != 0) flags = 0;
+    }
+    g.b1 |= flags;
+  }
+}
+
 template <typename T>
 int build_tile_segment_absorbed(uint32_t n, const std::vector<const TileItem*>& seg, std::vector<uint32_t> high, TileSegmentPlan<T>* out,
                                 int order_rule, TileAbsorbedX* ab) {
@@ -697,6 +727,7 @@ int build_tile_segment_absorbed(uint32_t n, const std::vector<const TileItem*>& 
     flip |= 1u << (tile_is_low(p, out->p5) ? tile_low_bit(p) : (uint32_t)kTileLow + (uint32_t)(f - out->high.begin()));
   }
   out->pd.flip = flip;
+  tile_mark_sign_rows<T>(&out->gates);
   return QIP_OK;
 }
 template int build_tile_segment_absorbed<double>(uint32_t, const std::vector<const TileItem*>&, std::vector<uint32_t>, TileSegmentPlan<double>*, int, TileAbsorbedX*);

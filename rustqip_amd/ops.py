@@ -317,6 +317,9 @@ def debug_sparse_tile(n: int, op, dtype: int = _ffi.QIP_C64) -> dict:
 
 
 TILE_PLAN_INTERP, TILE_PLAN_ABSORB_X = 1024, 4096  # mode bits of debug_tile_plan
+# "b1" of a dense 1-qubit item (kind 0) in the "absorb" lists of debug_tile_plan, beside 1 = real entries and 2 = X (csrc/qip_kernels.h
+# TileGate, kTileSignRows / kTileSignNeg0 / kTileSignNeg1): row 1 is row 0 up to one sign per column; column 0 / 1 negated
+TILE_SIGN_ROWS, TILE_SIGN_NEG0, TILE_SIGN_NEG1 = 4, 8, 16
 
 
 def debug_tile_plan(n: int, ops, mode: int = 1, dtype: int = _ffi.QIP_C64) -> dict:
