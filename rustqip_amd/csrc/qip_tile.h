@@ -23,6 +23,15 @@ struct TileItem {
   // permutation of the index bits (launch_permute)
   std::vector<std::pair<uint32_t, uint32_t>> swap_pairs;
 };
+// The positions a tileable item exchanges amplitudes across — a dense target, both swap bits; a diagonal gate has none — which
+// are the positions that must be tile bits (controls and diagonal targets may stay outside).  Returns how many; the entries of
+// `out` behind them mean nothing.
+static inline int tile_exch(const TileItem& it, uint32_t out[3]) {
+  out[0] = it.t0;
+  out[1] = it.t1;
+  out[2] = it.t2;
+  return it.kind == 0 ? 1 : it.kind == 2 || it.kind == 3 ? 2 : it.kind == 4 ? 3 : 0;
+}
 
 // Everything the host decides about one segment before anything touches the device: which amplitude-index
 // positions the tile's free bits 6..10 stand for, the gate descriptors, the passes and each gate's resolution
@@ -125,7 +134,6 @@ template <typename T> struct WidePlan {
   std::vector<WidePass> passes;    // passes.back() may hold no gate: the way back to the load arrangement
   std::vector<uint32_t> order;
 };
-extern thread_local int t_tile_high;  // free positions per segment the scheduler plans for (kTileHigh, or kWideHigh in wide mode)
 template <typename T>
 int build_wide_segment(uint32_t n, const std::vector<const TileItem*>& seg, std::vector<uint32_t> high, WidePlan<T>* out, int order_rule = 0);
 

@@ -85,9 +85,8 @@ int classify_tile_item(int dtype, uint32_t n, const qip_op* op, TileItem* it) {
   if (it->tileable) {
     for (uint32_t c : p.cpos) it->d_mask |= 1ull << c;
     if (it->kind == 1) it->d_mask |= 1ull << it->t0;
-    else it->nd_mask |= 1ull << it->t0;
-    if (it->kind >= 2) it->nd_mask |= 1ull << it->t1;
-    if (it->kind == 4) it->nd_mask |= 1ull << it->t2;
+    uint32_t ex[3];
+    for (int e = 0, ne = tile_exch(*it, ex); e < ne; ++e) it->nd_mask |= 1ull << ex[e];
   } else {
     for (uint32_t b : it->pos) it->nd_mask |= 1ull << b;
   }
@@ -157,6 +156,47 @@ extern "C" int qip_hip_tile_lane_assignment(int dtype, const uint32_t* pass_bits
   return QIP_OK;
 } QIP_CATCH_ALL
 
+// ---- what the two segment builders (build_tile_segment, build_wide_segment) have in common ----
+
+// free positions from `from` upwards that are neither rows nor claimed join `high` until it has `size` of them
+static void seg_pad_high(std::vector<uint32_t>* high, size_t size, uint32_t from, uint32_t n, uint32_t p5) {
+  for (uint32_t p = from; high->size() < size && p < n; ++p)
+    if (!tile_is_low(p, p5) && std::find(high->begin(), high->end(), p) == high->end()) high->push_back(p);
+}
+
+// per position, how many of the segment's items exchange amplitudes across it
+static std::vector<uint32_t> seg_exch_uses(const std::vector<const TileItem*>& seg) {
+  std::vector<uint32_t> uses(64, 0);
+  for (const TileItem* it : seg) {
+    uint32_t ex[3];
+    for (int e = 0, ne = tile_exch(*it, ex); e < ne; ++e) uses[ex[e]] += 1;
+  }
+  return uses;
+}
+
+// The order the gates of a segment (at most 256) must keep among themselves, under the commutation relation the scheduler itself
+// uses: two gates commute when on every shared bit both only TEST it; order_rule 1 (tile = 1) additionally needs one of the two
+// rounding-free, which keeps every amplitude's sequence of rounded operations — the result stays IEEE-equal to circuit order.
+struct SegDeps {
+  typedef std::array<uint64_t, 4> Set;  // a set of the segment's gates
+  static bool has(const Set& m, size_t j) { return (m[j >> 6] >> (j & 63)) & 1ull; }
+  static void put(Set& m, size_t j) { m[j >> 6] |= 1ull << (j & 63); }
+  std::vector<Set> preds;  // the earlier gates that gate j may not overtake
+  SegDeps(const std::vector<const TileItem*>& seg, int order_rule) : preds(seg.size(), Set{0, 0, 0, 0}) {
+    for (size_t j = 0; j < seg.size(); ++j)
+      for (size_t i = 0; i < j; ++i) {
+        const TileItem &a = *seg[i], &b = *seg[j];
+        const bool commute = !(b.nd_mask & (a.nd_mask | a.d_mask)) && !(b.d_mask & a.nd_mask);
+        if (!commute || (order_rule < 2 && !a.exact && !b.exact)) put(preds[j], i);
+      }
+  }
+  bool ready(const Set& placed, size_t j) const {  // not placed yet, every predecessor placed
+    if (has(placed, j)) return false;
+    for (int w = 0; w < 4; ++w)
+      if (preds[j][w] & ~placed[w]) return false;
+    return true;
+  }
+};
 
 template <typename T>
 int build_tile_segment(uint32_t n, bool passes, const std::vector<const TileItem*>& seg_in,
@@ -178,21 +218,11 @@ int build_tile_segment(uint32_t n, bool passes, const std::vector<const TileItem
   if (p5 == 5u && g_tile_pad_from > kTileLow && high.size() < (size_t)kTileHigh && n > 7 && std::find(high.begin(), high.end(), 6u) != high.end() &&
       std::find(high.begin(), high.end(), 7u) == high.end())
     high.push_back(7u);
-  for (uint32_t p = std::max<uint32_t>(pad_from, kTileLow); high.size() < (size_t)kTileHigh && p < n; ++p)
-    if (!tile_is_low(p, p5) && std::find(high.begin(), high.end(), p) == high.end()) high.push_back(p);
-  for (uint32_t p = 5; high.size() < (size_t)kTileHigh && p < n; ++p)
-    if (!tile_is_low(p, p5) && std::find(high.begin(), high.end(), p) == high.end()) high.push_back(p);
+  seg_pad_high(&high, kTileHigh, std::max<uint32_t>(pad_from, kTileLow), n, p5);
+  seg_pad_high(&high, kTileHigh, 5, n, p5);
   // the first kTileWaveBits free positions are wave bits at load / store time, the last three are the lane's own
   // elements: give the free positions that are exchange targets least often to the wave bits
-  std::vector<uint32_t> uses(64, 0);
-  for (const TileItem* it : seg) {
-    if (it->kind == 0) uses[it->t0] += 1;
-    if (it->kind >= 2) {
-      uses[it->t0] += 1;
-      uses[it->t1] += 1;
-    }
-    if (it->kind == 4) uses[it->t2] += 1;
-  }
+  const std::vector<uint32_t> uses = seg_exch_uses(seg);
   if (g_tile_wave_rule == 1) std::sort(high.begin(), high.end());                                  // lowest positions = wave bits
   else if (g_tile_wave_rule == 2) std::sort(high.begin(), high.end(), std::greater<uint32_t>());  // highest positions = wave bits
   else std::stable_sort(high.begin(), high.end(), [&](uint32_t a, uint32_t b) { return uses[a] < uses[b]; });
@@ -203,34 +233,20 @@ int build_tile_segment(uint32_t n, bool passes, const std::vector<const TileItem
   };
   if (passes && order_rule >= 1 && g_tile_sched != 0 && seg.size() >= 3 && seg.size() <= 256) {
     const size_t N = seg.size();
-    typedef std::array<uint64_t, 4> Set;  // a set of the segment's gates
-    auto has = [](const Set& m, size_t j) { return (m[j >> 6] >> (j & 63)) & 1ull; };
-    auto put = [](Set& m, size_t j) { m[j >> 6] |= 1ull << (j & 63); };
+    typedef SegDeps::Set Set;
     std::vector<uint32_t> ex(N, 0), full(N, 0);  // masks over the tile's eleven bits: exchange bits; those plus the in-tile controls when three slots allow
     for (size_t i = 0; i < N; ++i) {
       const TileItem& it = *seg[i];
-      uint32_t e = 0, c = 0;
-      if (it.kind == 0) e = 1u << tile_bit(it.t0);
-      if (it.kind == 2 || it.kind == 3) e = (1u << tile_bit(it.t0)) | (1u << tile_bit(it.t1));
-      if (it.kind == 4) e = (1u << tile_bit(it.t0)) | (1u << tile_bit(it.t1)) | (1u << tile_bit(it.t2));
+      uint32_t e = 0, c = 0, pos[3];
+      for (int k = 0, ne = tile_exch(it, pos); k < ne; ++k) e |= 1u << tile_bit(pos[k]);
       for (uint32_t cp : it.cpos)
         if (tile_bit(cp) != kTileOutside) c |= 1u << tile_bit(cp);
       ex[i] = e;
       full[i] = e && __builtin_popcount(e | c) <= 3 ? (e | c) : e;
     }
-    std::vector<Set> preds(N, Set{0, 0, 0, 0});
-    for (size_t j = 0; j < N; ++j)
-      for (size_t i = 0; i < j; ++i) {
-        const TileItem &a = *seg[i], &b = *seg[j];
-        const bool commute = !(b.nd_mask & (a.nd_mask | a.d_mask)) && !(b.d_mask & a.nd_mask);
-        if (!commute || (order_rule < 2 && !a.exact && !b.exact)) put(preds[j], i);
-      }
-    auto ready = [&](const Set& placed, size_t j) {
-      if (has(placed, j)) return false;
-      for (int w = 0; w < 4; ++w)
-        if (preds[j][w] & ~placed[w]) return false;
-      return true;
-    };
+    const SegDeps deps(seg, order_rule);
+    auto put = SegDeps::put;
+    auto ready = [&](const Set& placed, size_t j) { return deps.ready(placed, j); };
     // the grouping rule of the pass table below, as a count
     auto count_passes = [&](const std::vector<size_t>& sq) {
       uint32_t open = 0;
@@ -434,10 +450,11 @@ int build_tile_segment(uint32_t n, bool passes, const std::vector<const TileItem
       bits.clear();
     };
     for (uint32_t i = 0; i < (uint32_t)gates.size(); ++i) {
-      std::vector<uint32_t> add;
-      if (gates[i].kind == 0) add = {gates[i].b0};
-      if (gates[i].kind == 2 || gates[i].kind == 3) add = {gates[i].b0, gates[i].b1};
-      if (gates[i].kind == 4) add = {gates[i].b0, gates[i].b1, gates[i].tpos_out};  // exactly the pass
+      std::vector<uint32_t> bare;  // the gate's exchange bits
+      if (gates[i].kind == 0) bare = {gates[i].b0};
+      if (gates[i].kind == 2 || gates[i].kind == 3) bare = {gates[i].b0, gates[i].b1};
+      if (gates[i].kind == 4) bare = {gates[i].b0, gates[i].b1, gates[i].tpos_out};  // exactly the pass
+      std::vector<uint32_t> add = bare;
       if (!add.empty()) {
         // a control of a dense gate / swap is a scalar branch on a pass bit but a per-lane select on a lane
         // bit (k_tile_passes): make the in-tile controls pass bits too whenever the three slots allow
@@ -453,13 +470,8 @@ int build_tile_segment(uint32_t n, bool passes, const std::vector<const TileItem
         return m;
       };
       std::vector<uint32_t> merged = merge(add);
-      if (merged.size() > 3 && !add.empty()) {  // the controls were optional: the exchange bits alone may still fit the open pass
-        std::vector<uint32_t> bare;
-        if (gates[i].kind == 0) bare = {gates[i].b0};
-        if (gates[i].kind == 2 || gates[i].kind == 3) bare = {gates[i].b0, gates[i].b1};
-        if (gates[i].kind == 4) bare = {gates[i].b0, gates[i].b1, gates[i].tpos_out};
-        if (merge(bare).size() <= 3) merged = merge(bare);
-      }
+      // the controls were optional: the exchange bits alone may still fit the open pass
+      if (merged.size() > 3 && !add.empty() && merge(bare).size() <= 3) merged = merge(bare);
       if (merged.size() > 3) {
         close_pass(i);
         merged = add;
@@ -749,22 +761,12 @@ int build_wide_segment(uint32_t n, const std::vector<const TileItem*>& seg_in, s
   out->p5 = p5;
   if (n < (uint32_t)kWideBits) return fail(QIP_ERR_UNSUPPORTED, "wide tiles need n >= %d", kWideBits);
   const uint32_t pad_from = std::min<uint32_t>((uint32_t)g_tile_pad_from, n > (uint32_t)kWideBits ? n - 7 : 5u);
-  for (uint32_t p = std::max<uint32_t>(pad_from, 5u); high.size() < (size_t)kWideHigh && p < n; ++p)
-    if (!tile_is_low(p, p5) && std::find(high.begin(), high.end(), p) == high.end()) high.push_back(p);
-  for (uint32_t p = 5; high.size() < (size_t)kWideHigh && p < n; ++p)
-    if (!tile_is_low(p, p5) && std::find(high.begin(), high.end(), p) == high.end()) high.push_back(p);
+  seg_pad_high(&high, kWideHigh, std::max<uint32_t>(pad_from, 5u), n, p5);
+  seg_pad_high(&high, kWideHigh, 5, n, p5);
   if (high.size() != (size_t)kWideHigh) return fail(QIP_ERR_UNSUPPORTED, "a wide segment with %zu high positions", high.size());
   // the two positions that are exchange targets least often become the wave bits (tile bits 6, 7): the five others are
   // register bits from the start
-  std::vector<uint32_t> uses(64, 0);
-  for (const TileItem* it : seg) {
-    if (it->kind == 0) uses[it->t0] += 1;
-    if (it->kind >= 2) {
-      uses[it->t0] += 1;
-      uses[it->t1] += 1;
-    }
-    if (it->kind == 4) uses[it->t2] += 1;
-  }
+  const std::vector<uint32_t> uses = seg_exch_uses(seg);
   std::sort(high.begin(), high.end());
   std::stable_sort(high.begin(), high.end(), [&](uint32_t a, uint32_t b) { return uses[a] < uses[b]; });
   std::sort(high.begin(), high.begin() + 2);
@@ -780,9 +782,8 @@ int build_wide_segment(uint32_t n, const std::vector<const TileItem*>& seg_in, s
   const Bits load_bits = {8, 9, 10, 11, 12};
   auto item_exch = [&](const TileItem& it) {
     Bits e;
-    if (it.kind == 0) e = {tile_bit(it.t0)};
-    if (it.kind == 2 || it.kind == 3) e = {tile_bit(it.t0), tile_bit(it.t1)};
-    if (it.kind == 4) e = {tile_bit(it.t0), tile_bit(it.t1), tile_bit(it.t2)};
+    uint32_t pos[3];
+    for (int k = 0, ne = tile_exch(it, pos); k < ne; ++k) e.push_back(tile_bit(pos[k]));
     return e;
   };
   // The register sets a given gate order leads to.  At a gate whose exchange bits are not all register bits the tile is
@@ -853,31 +854,15 @@ int build_wide_segment(uint32_t n, const std::vector<const TileItem*>& seg_in, s
     return arr;
   };
   // The order of the gates inside the segment (order_rule 1 / 2 = the "tile" option, as in build_tile_segment): list scheduling
-  // over the scheduler's own commutation relation — two gates commute when on every shared bit both only test it; tile = 1
-  // additionally needs one of the two rounding-free, which keeps every amplitude's sequence of rounded operations — emits
-  // every ready gate that fits the register set before it transposes, and transposes for the ready gate that needs the
-  // fewest new bits.  Adopted only where it saves transpositions.
+  // over the same relation (SegDeps) emits every ready gate that fits the register set before it transposes, and transposes
+  // for the ready gate that needs the fewest new bits.  Adopted only where it saves transpositions.
   if (order_rule >= 1 && g_tile_sched != 0 && seg.size() >= 3 && seg.size() <= 256) {
     const size_t NG = seg.size();
-    typedef std::array<uint64_t, 4> Set;
-    auto sget = [](const Set& m, size_t j) { return (m[j >> 6] >> (j & 63)) & 1ull; };
-    auto sput = [](Set& m, size_t j) { m[j >> 6] |= 1ull << (j & 63); };
-    std::vector<Set> preds(NG, Set{0, 0, 0, 0});
-    for (size_t j = 0; j < NG; ++j)
-      for (size_t i = 0; i < j; ++i) {
-        const TileItem &a = *seg[i], &b = *seg[j];
-        const bool commute = !(b.nd_mask & (a.nd_mask | a.d_mask)) && !(b.d_mask & a.nd_mask);
-        if (!commute || (order_rule < 2 && !a.exact && !b.exact)) sput(preds[j], i);
-      }
+    const SegDeps deps(seg, order_rule);
     std::vector<Bits> ex(NG);
     for (size_t i = 0; i < NG; ++i) ex[i] = item_exch(*seg[i]);
-    Set placed{0, 0, 0, 0};
-    auto ready = [&](size_t j) {
-      if (sget(placed, j)) return false;
-      for (int w = 0; w < 4; ++w)
-        if (preds[j][w] & ~placed[w]) return false;
-      return true;
-    };
+    SegDeps::Set placed{0, 0, 0, 0};
+    auto ready = [&](size_t j) { return deps.ready(placed, j); };
     std::vector<size_t> ord;
     Bits R = load_bits;
     while (ord.size() < NG) {
@@ -887,7 +872,7 @@ int build_wide_segment(uint32_t n, const std::vector<const TileItem*>& seg_in, s
         bool fits = true;
         for (uint32_t t : ex[j]) fits = fits && has(R, t);
         if (fits) {
-          sput(placed, j);
+          SegDeps::put(placed, j);
           ord.push_back(j);
           progressed = true;
         }
@@ -924,7 +909,7 @@ int build_wide_segment(uint32_t n, const std::vector<const TileItem*>& seg_in, s
         if (has(newR, t)) continue;
         size_t nu = NG + (has(load_bits, t) ? 0 : 1);
         for (size_t j = 0; j < NG; ++j)
-          if (!sget(placed, j) && has(ex[j], t)) {
+          if (!SegDeps::has(placed, j) && has(ex[j], t)) {
             nu = j;
             break;
           }
@@ -1068,55 +1053,79 @@ template int build_wide_segment<double>(uint32_t, const std::vector<const TileIt
 template int build_wide_segment<float>(uint32_t, const std::vector<const TileItem*>&, std::vector<uint32_t>, WidePlan<float>*, int);
 
 // ---------------------------------------------------------------------------------------
-// Which five positions should a segment claim?  First come, first served (the scan below claims positions in the order the
-// circuit asks for them) spends them on whatever the next few gates touch.  The gain rule looks at what each position
-// would BUY: starting from the positions the head gate needs, it repeatedly claims the free
-// position that lets the most further gates join this segment (a dry run of the same scan with the claimed set frozen;
-// gates that exchange amplitudes count 1, diagonal ones — which never need a position — a little), until five are claimed
-// or no single position adds anything; what is left is claimed first-come as before.  Host arithmetic only, and the
-// schedule's invariants do not depend on it: every gate still joins under the commutation / exactness rules of the scan.
+// Growing a segment.  A segment is grown from its first op, scanning ahead.  A later gate may join over the gates skipped so
+// far only if it commutes with each of them — on every bit they share, both gates only TEST the bit (control or diagonal
+// target), neither exchanges amplitudes across it — and, unless `reorder` (which accepts rounding-level differences), the
+// commutation is EXACT: the gate itself, or every skipped gate, is rounding-free (entries in {0, +-1, +-i}: X, Y, Z, S, CNOT,
+// CZ, Toffoli, SWAP ...).  Exact commutations leave every amplitude's sequence of rounded operations unchanged, so the result
+// stays IEEE-equal to circuit order.  Only the positions a gate exchanges amplitudes across (tile_exch) must be tile bits.
+//
+// Which positions should a segment claim?  First come, first served (the scan claims positions in the order the circuit asks
+// for them) spends them on whatever the next few gates touch.  The gain rule looks at what each position would BUY: starting
+// from the positions the head gate needs, it repeatedly claims the free position that lets the most further gates join this
+// segment (a dry run of the scan with the claimed set frozen; gates that exchange amplitudes count 1, diagonal ones — which
+// never need a position — a little), until every free position is claimed or no single position adds anything; what is left is
+// claimed first-come as before.  Host arithmetic only, and the schedule's invariants do not depend on it: every gate still
+// joins under the commutation / exactness rules of the scan.
 // ---------------------------------------------------------------------------------------
-thread_local int t_tile_high = kTileHigh;  // make_tile_schedule sets it from the mode (bit 4: wide tiles, kWideHigh)
-static thread_local int t_seg_rule = 0;  // the rule in force for the plan being made (make_tile_schedule tries several)
+struct SchedRules {
+  uint32_t free;  // free positions per segment: kTileHigh, or kWideHigh for wide tiles
+  int claim;      // how a segment claims them: 0 = first come, 1 / 3 = the gain rule with a diagonal gate weighing 0.125 / 0.5
+};
 struct SegScan {
   const std::vector<TileItem>& L;
   const std::vector<char>& done;
   uint64_t count, window;
-  bool reorder, relabel;
+  bool reorder, relabel;  // relabel: uncontrolled Swap ops met before anything was skipped are label exchanges, not gates
   size_t max_ops, max_exch;
   uint32_t p5;  // position of tile bit 5: which positions are free of charge (tile_is_low)
+  SchedRules rules;
 };
 
-// weight of the gates that join a segment grown from `head` when exactly the positions `H` may be used above the rows
-static double seg_dry_run(const SegScan& c, uint64_t head, std::vector<uint32_t> phys, const std::vector<uint32_t>& H) {
-  uint64_t blocked_nd = 0, blocked_d = 0;
-  bool skipped_inexact = false, any_skipped = false;
-  size_t joined = 0, exch_gates = 0;
-  double w = 0;
+// the positions a tile holds: its rows and the claimed ones
+static uint64_t seg_tile_mask(uint32_t p5, const std::vector<uint32_t>& high) {
+  uint64_t tile = tile_low_mask(p5);
+  for (uint32_t p : high) tile |= 1ull << p;
+  return tile;
+}
+
+// THE scan: the ops from `head` on that join its segment, in order.  `phys` maps an item's positions to the positions the tile
+// test is about (the identity without relabelling); `tile` is the set of positions the tile holds (seg_tile_mask), which may
+// grow by `room` more (0: frozen).  join(i, claimed, n) -> int (an error ends the scan) is called for every op that joins, with
+// the positions it made the tile claim; absorb(i) for every swap that becomes a label exchange (it may change `phys`); marking
+// ops done is theirs.  No allocation: the dry run below is called O(n · free positions) times per segment.
+template <typename Join, typename Absorb>
+static int seg_scan(const SegScan& c, uint64_t head, const std::vector<uint32_t>& phys, uint64_t tile, size_t room, Join join, Absorb absorb) {
+  uint64_t blocked_nd = 0, blocked_d = 0;  // bits the skipped gates exchange across / only test
+  bool skipped_inexact = false;            // some skipped gate rounds
+  bool any_skipped = false;
+  size_t joined = 0, exch_gates = 0;  // exch_gates: gates that may open a pass (max_exch bounds the pass table)
   for (uint64_t i = head; i < c.count && i <= head + (any_skipped ? c.window : c.count) && joined < c.max_ops; ++i) {
     if (c.done[i]) continue;
     const TileItem& it = c.L[i];
-    if (c.relabel && !any_skipped && !it.swap_pairs.empty()) {
-      for (const auto& pr : it.swap_pairs) std::swap(phys[pr.first], phys[pr.second]);
+    if (c.relabel && !any_skipped && !it.swap_pairs.empty()) {  // in circuit order, nothing pending before it
+      absorb(i);
       continue;
     }
     const bool commutes = !(it.nd_mask & (blocked_nd | blocked_d)) && !(it.d_mask & blocked_nd);
     bool fits = it.tileable && commutes && (c.reorder || it.exact || !skipped_inexact) && (it.kind == 1 || exch_gates < c.max_exch);
+    uint32_t claim[3], nclaim = 0;  // the positions the tile has to claim for it, in the order the item names them
+    uint64_t with = tile;
     if (fits) {
       uint32_t exch[3];
-      int ne = 0;
-      if (it.kind == 0) exch[ne++] = it.t0;
-      if (it.kind == 2 || it.kind == 3) { exch[ne++] = it.t0; exch[ne++] = it.t1; }
-      if (it.kind == 4) { exch[ne++] = it.t0; exch[ne++] = it.t1; exch[ne++] = it.t2; }
-      for (int e = 0; e < ne && fits; ++e) {
+      for (int e = 0, ne = tile_exch(it, exch); e < ne; ++e) {
         const uint32_t pp = phys[exch[e]];
-        fits = tile_is_low(pp, c.p5) || std::find(H.begin(), H.end(), pp) != H.end();
+        if (!((with >> pp) & 1ull)) claim[nclaim++] = pp;
+        with |= 1ull << pp;
       }
+      fits = nclaim <= room;
     }
     if (fits) {
+      tile = with;
+      room -= nclaim;
+      QCHK(join(i, claim, nclaim));
       joined += 1;
       exch_gates += it.kind != 1;
-      w += it.kind != 1 ? 1.0 : (t_seg_rule == 3 ? 0.5 : 0.125);
     } else {
       blocked_nd |= it.nd_mask;
       blocked_d |= it.d_mask;
@@ -1124,26 +1133,36 @@ static double seg_dry_run(const SegScan& c, uint64_t head, std::vector<uint32_t>
       any_skipped = true;
     }
   }
+  return QIP_OK;
+}
+
+// weight of the gates that join a segment grown from `head` when exactly the positions `H` may be used above the rows
+static double seg_dry_run(const SegScan& c, uint64_t head, const std::vector<uint32_t>& phys, const std::vector<uint32_t>& H) {
+  std::vector<uint32_t> trial;  // the labels as the swaps this run absorbs leave them
+  if (c.relabel) trial = phys;
+  double w = 0;
+  seg_scan(
+      c, head, c.relabel ? trial : phys, seg_tile_mask(c.p5, H), 0,
+      [&](uint64_t i, const uint32_t*, uint32_t) {
+        w += c.L[i].kind != 1 ? 1.0 : (c.rules.claim == 3 ? 0.5 : 0.125);
+        return (int)QIP_OK;
+      },
+      [&](uint64_t i) {
+        for (const auto& pr : c.L[i].swap_pairs) std::swap(trial[pr.first], trial[pr.second]);
+      });
   return w;
 }
 
 static std::vector<uint32_t> seg_choose_high(const SegScan& c, uint64_t head, const std::vector<uint32_t>& phys, uint32_t n) {
   std::vector<uint32_t> H;
-  if (t_seg_rule == 0) return H;
-  {
-    const TileItem& it = c.L[head];
-    uint32_t exch[3];
-    int ne = 0;
-    if (it.kind == 0) exch[ne++] = it.t0;
-    if (it.kind == 2 || it.kind == 3) { exch[ne++] = it.t0; exch[ne++] = it.t1; }
-    if (it.kind == 4) { exch[ne++] = it.t0; exch[ne++] = it.t1; exch[ne++] = it.t2; }
-    for (int e = 0; e < ne; ++e) {
-      const uint32_t pp = phys[exch[e]];
-      if (!tile_is_low(pp, c.p5) && std::find(H.begin(), H.end(), pp) == H.end()) H.push_back(pp);
-    }
+  if (c.rules.claim == 0) return H;
+  uint32_t exch[3];
+  for (int e = 0, ne = tile_exch(c.L[head], exch); e < ne; ++e) {
+    const uint32_t pp = phys[exch[e]];
+    if (!tile_is_low(pp, c.p5) && std::find(H.begin(), H.end(), pp) == H.end()) H.push_back(pp);
   }
   double base = seg_dry_run(c, head, phys, H);
-  while (H.size() < (size_t)t_tile_high) {
+  while (H.size() < (size_t)c.rules.free) {
     int best = -1;
     double best_w = base;
     for (uint32_t pp = 5; pp < n; ++pp) {
@@ -1163,40 +1182,47 @@ static std::vector<uint32_t> seg_choose_high(const SegScan& c, uint64_t head, co
   return H;
 }
 
-
-// Pure host scheduling (no device, no launches).  Invariants, checked by tests/test_host_ops.py through
-// qip_hip_plan_tiles: every op appears in exactly one step; an op only overtakes ops it commutes with (on every
-// shared bit both only test it); without `reorder` only when it, or every op it overtakes, is rounding-free.
-int schedule_tiles(int dtype, uint32_t n, const qip_op* ops, uint64_t count, bool reorder,
-                          std::vector<TileItem>* items_out, std::vector<TileStep>* steps, bool allow_2q = true,
-                          bool allow_permute = true, const std::vector<char>* alone = nullptr) {
-  std::vector<TileItem>& items = *items_out;
-  items.assign(count, TileItem());
+// the caller's ops as tile items (2- / 3-qubit dense items only where the kernel that will run them has the form)
+static int classify_tile_items(int dtype, uint32_t n, const qip_op* ops, uint64_t count, bool allow_2q, std::vector<TileItem>* items) {
+  items->assign(count, TileItem());
   for (uint64_t i = 0; i < count; ++i) {
-    int rc = classify_tile_item(dtype, n, &ops[i], &items[i]);
+    int rc = classify_tile_item(dtype, n, &ops[i], &(*items)[i]);
     if (rc != QIP_OK) {
       std::string msg = g_last_error;
       return fail(rc, "op %llu: %s", (unsigned long long)i, msg.c_str());
     }
-    if (items[i].kind >= 3 && !allow_2q) items[i].tileable = false;  // k_tile_gates has no 2- / 3-qubit form
-    if (alone && (*alone)[i]) {  // no tile item, and nothing overtakes it: it exchanges across every bit as far as the scan knows
+    if ((*items)[i].kind >= 3 && !allow_2q) (*items)[i].tileable = false;  // k_tile_gates has no 2- / 3-qubit form
+  }
+  return QIP_OK;
+}
+
+// Pure host scheduling (no device, no launches).  Invariants, checked by tests/test_host_ops.py through
+// qip_hip_plan_tiles: every op appears in exactly one step; an op only overtakes ops it commutes with (on every
+// shared bit both only test it); without `reorder` only when it, or every op it overtakes, is rounding-free.
+static int schedule_tiles(int dtype, uint32_t n, const qip_op* ops, uint64_t count, bool reorder, SchedRules rules, std::vector<TileItem>* items_out,
+                          std::vector<TileStep>* steps, bool allow_2q = true, bool allow_permute = true, const std::vector<char>* alone = nullptr) {
+  std::vector<TileItem>& items = *items_out;
+  QCHK(classify_tile_items(dtype, n, ops, count, allow_2q, &items));
+  for (uint64_t i = 0; alone && i < count; ++i)
+    if ((*alone)[i]) {  // no tile item, and nothing overtakes it: it exchanges across every bit as far as the scan knows
       items[i].tileable = false;
       items[i].nd_mask = ~0ull;
       items[i].d_mask = 0;
     }
-  }
   std::vector<char> done(count, 0);
   uint64_t head = 0;
-  const uint64_t window = 256;
   const uint32_t p5 = tile_p5(dtype, n);
+  std::vector<uint32_t> ident(n);
+  for (uint32_t b = 0; b < n; ++b) ident[b] = b;
+  const SegScan sc{items, done, count, 256, reorder, false, (size_t)kTileMaxGates, (size_t)kTileMaxExchGates, p5, rules};
   while (head < count) {
     if (done[head]) {
       ++head;
       continue;
     }
-    // A run of uncontrolled Swap ops that one segment cannot hold (more than kTileHigh of the moved positions lie above
-    // the tile's fixed low bits — QFT's closing bit reversal is 15 transpositions over all 30 positions) composes to one
-    // permutation of the index bits and goes as ONE out-of-place sweep.  Swaps only move amplitudes, so this is
+    // A run of uncontrolled Swap ops that one segment cannot hold (more of the moved positions than a segment has free ones
+    // lie above the tile's fixed low bits — QFT's closing bit reversal is 15 transpositions over all 30 positions) composes
+    // to one permutation of the index bits and goes as ONE out-of-place sweep.  Swaps only move amplitudes, so this is
     // bit-identical to applying them one by one.  Ops of the run that an earlier segment already hoisted are skipped:
     // the hoist was only legal because they commute with everything in between.
     if (allow_permute && !items[head].swap_pairs.empty()) {
@@ -1219,7 +1245,7 @@ int schedule_tiles(int dtype, uint32_t n, const qip_op* ops, uint64_t count, boo
         run.perm = next;
         run.ops.push_back(j);
       }
-      if (run.ops.size() >= 2 && __builtin_popcountll(moved & ~tile_low_mask(p5)) > t_tile_high) {
+      if (run.ops.size() >= 2 && (uint32_t)__builtin_popcountll(moved & ~tile_low_mask(p5)) > rules.free) {
         for (uint64_t i : run.ops) done[i] = 1;
         steps->push_back(run);
         continue;
@@ -1230,55 +1256,17 @@ int schedule_tiles(int dtype, uint32_t n, const qip_op* ops, uint64_t count, boo
       done[head++] = 1;
       continue;
     }
-    // Grow a segment from `head`, scanning ahead.  A later gate may join over the gates skipped so far only if
-    // it commutes with each of them — on every bit they share, both gates only TEST the bit (control or diagonal
-    // target), neither exchanges amplitudes across it — and, unless `reorder` (which accepts rounding-level
-    // differences), the commutation is EXACT: the gate itself, or every skipped gate, is rounding-free
-    // (entries in {0, +-1, +-i}: X, Y, Z, S, CNOT, CZ, Toffoli, SWAP ...).  Exact commutations leave every
-    // amplitude's sequence of rounded operations unchanged, so the result stays IEEE-equal to circuit order.
     TileStep st;
-    {
-      std::vector<uint32_t> ident(n);
-      for (uint32_t b = 0; b < n; ++b) ident[b] = b;
-      const SegScan sc{items, done, count, window, reorder, false, (size_t)kTileMaxGates, (size_t)kTileMaxExchGates, p5};
-      st.high = seg_choose_high(sc, head, ident, n);
-    }
-    uint64_t blocked_nd = 0, blocked_d = 0;  // bits the skipped gates exchange across / only test
-    bool skipped_inexact = false;            // some skipped gate rounds
-    bool any_skipped = false;
-    size_t exch_gates = 0;  // gates that may open a pass (kTileMaxExchGates bounds the pass table)
-    for (uint64_t i = head; i < count && i <= head + (any_skipped ? window : count) && st.ops.size() < (size_t)kTileMaxGates; ++i) {
-      if (done[i]) continue;
-      const TileItem& it = items[i];
-      const bool commutes = !(it.nd_mask & (blocked_nd | blocked_d)) && !(it.d_mask & blocked_nd);
-      bool fits = it.tileable && commutes && (reorder || it.exact || !skipped_inexact) &&
-                  (it.kind == 1 || exch_gates < (size_t)kTileMaxExchGates);
-      std::vector<uint32_t> need;
-      if (fits) {
-        // only bits the gate exchanges amplitudes across must be tile bits: a dense target, both swap bits;
-        // controls and diagonal targets may stay outside (block-uniform predicates)
-        std::vector<uint32_t> exch;
-        if (it.kind == 0) exch = {it.t0};
-        if (it.kind == 2 || it.kind == 3) exch = {it.t0, it.t1};
-        if (it.kind == 4) exch = {it.t0, it.t1, it.t2};
-        for (uint32_t p : exch)
-          if (!tile_is_low(p, p5) && std::find(st.high.begin(), st.high.end(), p) == st.high.end() &&
-              std::find(need.begin(), need.end(), p) == need.end())
-            need.push_back(p);
-        fits = st.high.size() + need.size() <= (size_t)t_tile_high;
-      }
-      if (fits) {
-        for (uint32_t p : need) st.high.push_back(p);
-        st.ops.push_back(i);
-        done[i] = 1;
-        exch_gates += it.kind != 1;
-      } else {
-        blocked_nd |= it.nd_mask;
-        blocked_d |= it.d_mask;
-        skipped_inexact = skipped_inexact || !it.exact;
-        any_skipped = true;
-      }
-    }
+    st.high = seg_choose_high(sc, head, ident, n);
+    QCHK(seg_scan(
+        sc, head, ident, seg_tile_mask(p5, st.high), rules.free - st.high.size(),
+        [&](uint64_t i, const uint32_t* claimed, uint32_t nclaimed) {
+          st.high.insert(st.high.end(), claimed, claimed + nclaimed);
+          st.ops.push_back(i);
+          done[i] = 1;
+          return (int)QIP_OK;
+        },
+        [](uint64_t) {}));
     steps->push_back(st);
   }
   return QIP_OK;
@@ -1298,20 +1286,13 @@ int schedule_tiles(int dtype, uint32_t n, const qip_op* ops, uint64_t count, boo
 // configs[1] at n = 30 (256 gates): 19 -> 13 + 1 sweeps; 1024 gates: 70 -> 47 + 1.
 // ---------------------------------------------------------------------------------------
 
-int schedule_tiles_relabel(int dtype, uint32_t n, const qip_op* ops, uint64_t count, bool reorder, bool allow_2q,
+static int schedule_tiles_relabel(int dtype, uint32_t n, const qip_op* ops, uint64_t count, bool reorder, SchedRules rules, bool allow_2q,
                                   TileSchedule* out) {
   // `out->init_phys` (optional): the layout the state is in when the schedule starts (a previous call left it relabelled);
   // `out->keep_layout`: do not close with the restoring permutation sweep — the final layout is returned in `final_phys`
   // and stays in force (option tile_relabel = 3: the layout persists across apply_ops calls)
-  std::vector<TileItem> L(count);  // the caller's ops, logical bit positions
-  for (uint64_t i = 0; i < count; ++i) {
-    int rc = classify_tile_item(dtype, n, &ops[i], &L[i]);
-    if (rc != QIP_OK) {
-      std::string msg = g_last_error;
-      return fail(rc, "op %llu: %s", (unsigned long long)i, msg.c_str());
-    }
-    if (L[i].kind >= 3 && !allow_2q) L[i].tileable = false;
-  }
+  std::vector<TileItem> L;  // the caller's ops, logical bit positions
+  QCHK(classify_tile_items(dtype, n, ops, count, allow_2q, &L));
   const uint32_t p5 = tile_p5(dtype, n);
   std::vector<uint32_t> phys(n);  // phys[p] = physical position of logical bit position p
   for (uint32_t p = 0; p < n; ++p) phys[p] = p;
@@ -1350,8 +1331,8 @@ int schedule_tiles_relabel(int dtype, uint32_t n, const qip_op* ops, uint64_t co
   };
   std::vector<char> done(count, 0);
   uint64_t head = 0;
-  const uint64_t window = 256;
-  const size_t max_circuit_ops = (size_t)kTileMaxGates - (size_t)kTileLow;  // room for the segment's closing swaps
+  // (kTileLow fewer ops and exchanging gates per segment: room for its closing swaps)
+  const SegScan sc{L, done, count, 256, reorder, true, (size_t)kTileMaxGates - (size_t)kTileLow, (size_t)kTileMaxExchGates - (size_t)kTileLow, p5, rules};
   while (head < count) {
     if (done[head]) {
       ++head;
@@ -1369,56 +1350,24 @@ int schedule_tiles_relabel(int dtype, uint32_t n, const qip_op* ops, uint64_t co
       done[head++] = 1;
       continue;
     }
-    // the segment: schedule_tiles' rules on the logical masks (commutation does not depend on names), the tile test on
-    // the physical positions
+    // the segment: the scan's rules on the logical masks (commutation does not depend on names), the tile test on the
+    // physical positions
     TileStep st;
-    {
-      const SegScan sc{L, done, count, window, reorder, true, max_circuit_ops, (size_t)kTileMaxExchGates - (size_t)kTileLow, p5};
-      st.high = seg_choose_high(sc, head, phys, n);
-    }
-    uint64_t blocked_nd = 0, blocked_d = 0;
-    bool skipped_inexact = false, any_skipped = false;
-    size_t joined = 0, exch_gates = 0;
-    for (uint64_t i = head; i < count && i <= head + (any_skipped ? window : count) && joined < max_circuit_ops; ++i) {
-      if (done[i]) continue;
-      const TileItem& it = L[i];
-      if (!any_skipped && !it.swap_pairs.empty()) {  // in circuit order, nothing pending before it: a label exchange
-        absorb(it);
-        done[i] = 1;
-        continue;
-      }
-      const bool commutes = !(it.nd_mask & (blocked_nd | blocked_d)) && !(it.d_mask & blocked_nd);
-      bool fits = it.tileable && commutes && (reorder || it.exact || !skipped_inexact) &&
-                  (it.kind == 1 || exch_gates < (size_t)kTileMaxExchGates - (size_t)kTileLow);  // (room for the closing swaps)
-      std::vector<uint32_t> need;
-      if (fits) {
-        std::vector<uint32_t> exch;
-        if (it.kind == 0) exch = {it.t0};
-        if (it.kind == 2 || it.kind == 3) exch = {it.t0, it.t1};
-        if (it.kind == 4) exch = {it.t0, it.t1, it.t2};
-        for (uint32_t p : exch) {
-          const uint32_t pp = phys[p];
-          if (!tile_is_low(pp, p5) && std::find(st.high.begin(), st.high.end(), pp) == st.high.end() &&
-              std::find(need.begin(), need.end(), pp) == need.end())
-            need.push_back(pp);
-        }
-        fits = st.high.size() + need.size() <= (size_t)t_tile_high;
-      }
-      if (fits) {
-        for (uint32_t pp : need) st.high.push_back(pp);
-        uint64_t at = 0;
-        QCHK(emit(i, &at));
-        st.ops.push_back(at);
-        done[i] = 1;
-        joined += 1;
-        exch_gates += it.kind != 1;
-      } else {
-        blocked_nd |= it.nd_mask;
-        blocked_d |= it.d_mask;
-        skipped_inexact = skipped_inexact || !it.exact;
-        any_skipped = true;
-      }
-    }
+    st.high = seg_choose_high(sc, head, phys, n);
+    QCHK(seg_scan(
+        sc, head, phys, seg_tile_mask(p5, st.high), rules.free - st.high.size(),
+        [&](uint64_t i, const uint32_t* claimed, uint32_t nclaimed) {
+          st.high.insert(st.high.end(), claimed, claimed + nclaimed);
+          uint64_t at = 0;
+          QCHK(emit(i, &at));
+          st.ops.push_back(at);
+          done[i] = 1;
+          return (int)QIP_OK;
+        },
+        [&](uint64_t i) {  // a label exchange
+          absorb(L[i]);
+          done[i] = 1;
+        }));
     // Who should live on positions 0..5 next?  Next amplitude-exchanging use of every qubit (ops not done yet, circuit
     // order).  First spend the tile's unclaimed free positions on the soonest-needed qubits outside the tile (they can
     // then be brought down as well), then bring the soonest-needed of the tile's qubits down, evicting the ones needed
@@ -1446,7 +1395,7 @@ int schedule_tiles_relabel(int dtype, uint32_t n, const qip_op* ops, uint64_t co
         if (nxt[p] != ~0ull) by_use.push_back(p);
       std::stable_sort(by_use.begin(), by_use.end(), [&](uint32_t a, uint32_t b) { return nxt[a] < nxt[b]; });
       for (uint32_t p : by_use) {
-        if (st.high.size() >= (size_t)t_tile_high) break;
+        if (st.high.size() >= (size_t)rules.free) break;
         if (!in_tile(phys[p])) st.high.push_back(phys[p]);
       }
       std::vector<uint32_t> tile_log;
@@ -1488,8 +1437,8 @@ int schedule_tiles_relabel(int dtype, uint32_t n, const qip_op* ops, uint64_t co
 
 // mode: bits 0-1 = the "tile" option (1 = circuit order, 2 = commuting reorder), bit 2 = relabel the qubits when that
 // shortens the plan, bit 3 = relabel unconditionally
-static int make_tile_schedule_rule(int dtype, uint32_t n, const qip_op* ops, uint64_t count, int mode, bool allow_2q, TileSchedule* out,
-                                   bool allow_permute, const std::vector<char>* alone) {
+static int make_tile_schedule_rule(int dtype, uint32_t n, const qip_op* ops, uint64_t count, int mode, SchedRules rules, bool allow_2q,
+                                   TileSchedule* out, bool allow_permute, const std::vector<char>* alone) {
   const bool reorder = (mode & 3) >= 2;
   bool start_identity = true;
   for (uint32_t p = 0; p < out->init_phys.size(); ++p) start_identity = start_identity && out->init_phys[p] == p;
@@ -1500,10 +1449,10 @@ static int make_tile_schedule_rule(int dtype, uint32_t n, const qip_op* ops, uin
     // state has no plain alternative short of restoring the order first (one sweep).
     const std::vector<uint32_t> init = out->init_phys;
     const bool keep = out->keep_layout;
-    QCHK(schedule_tiles_relabel(dtype, n, ops, count, reorder, allow_2q, out));
+    QCHK(schedule_tiles_relabel(dtype, n, ops, count, reorder, rules, allow_2q, out));
     if (!start_identity) return QIP_OK;
     TileSchedule plain;
-    QCHK(schedule_tiles(dtype, n, ops, count, reorder, &plain.items, &plain.steps, allow_2q));
+    QCHK(schedule_tiles(dtype, n, ops, count, reorder, rules, &plain.items, &plain.steps, allow_2q));
     if (out->steps.size() < plain.steps.size() || (mode & 8)) return QIP_OK;  // bit 3: keep it regardless (tests)
     *out = TileSchedule();
     out->init_phys = init;
@@ -1513,45 +1462,32 @@ static int make_tile_schedule_rule(int dtype, uint32_t n, const qip_op* ops, uin
   for (uint32_t p = 0; p < n; ++p) out->final_phys[p] = p;
   out->circuit = ops;
   out->count = count;
-  return schedule_tiles(dtype, n, ops, count, reorder, &out->items, &out->steps, allow_2q, allow_permute, alone);
+  return schedule_tiles(dtype, n, ops, count, reorder, rules, &out->items, &out->steps, allow_2q, allow_permute, alone);
 }
 
 // The plan under each rule for claiming a segment's positions (first come / what a position buys, two weights for the
 // diagonal gates), shortest kept: host arithmetic, microseconds per gate, against ~6 ms per sweep saved at n = 30.  Below
 // n = 24 a sweep costs less than the search: first come only.  Global option "tile_sched": 0 = first come only (and the
 // circuit's own gate order inside every segment), 1 = default, 2 = search at every size and in every mode (tests).
-static int make_tile_schedule_inner(int dtype, uint32_t n, const qip_op* ops, uint64_t count, int mode, bool allow_2q, TileSchedule* out,
-                                    bool allow_permute, const std::vector<char>* alone);
 int make_tile_schedule(int dtype, uint32_t n, const qip_op* ops, uint64_t count, int mode, bool allow_2q, TileSchedule* out,
                        bool allow_permute, const std::vector<char>* alone) {
   if (alone && ((mode & 4) || alone->size() != count)) return fail(QIP_ERR_INVALID, "internal error: ops kept alone need one flag per op and no relabelling");
   // mode bit 4: wide tiles (seven free positions per segment; a state of at least kWideBits + 1 qubits)
-  t_tile_high = ((mode & 16) && n > (uint32_t)kWideBits) ? kWideHigh : kTileHigh;
-  const int rc = make_tile_schedule_inner(dtype, n, ops, count, mode, allow_2q, out, allow_permute, alone);
-  t_tile_high = kTileHigh;
-  return rc;
-}
-static int make_tile_schedule_inner(int dtype, uint32_t n, const qip_op* ops, uint64_t count, int mode, bool allow_2q, TileSchedule* out,
-                                    bool allow_permute, const std::vector<char>* alone) {
+  SchedRules rules{(uint32_t)(((mode & 16) && n > (uint32_t)kWideBits) ? kWideHigh : kTileHigh), 0};
   // (only where gates may be reordered freely, tile = 2: in the IEEE-equal mode the sweeps are bound by f64 issue, a plan with
   // fewer, heavier sweeps is not faster there — Grover 15 -> 14 sweeps measured 2 % slower — and first come stays)
   const bool search = g_tile_sched != 0 && (n >= 24 || g_tile_sched == 2) && count >= 8 && ((mode & 3) >= 2 || g_tile_sched == 2);  // (2 = always: tests)
-  if (!search) {
-    t_seg_rule = 0;
-    return make_tile_schedule_rule(dtype, n, ops, count, mode, allow_2q, out, allow_permute, alone);
-  }
+  if (!search) return make_tile_schedule_rule(dtype, n, ops, count, mode, rules, allow_2q, out, allow_permute, alone);
   const std::vector<uint32_t> init = out->init_phys;
   const bool keep = out->keep_layout;
   TileSchedule best;
   bool have = false;
-  for (int rule : {0, 1, 3}) {
+  for (int claim : {0, 1, 3}) {
     TileSchedule cand;
     cand.init_phys = init;
     cand.keep_layout = keep;
-    t_seg_rule = rule;
-    const int rc = make_tile_schedule_rule(dtype, n, ops, count, mode, allow_2q, &cand, allow_permute, alone);
-    t_seg_rule = 0;
-    QCHK(rc);
+    rules.claim = claim;
+    QCHK(make_tile_schedule_rule(dtype, n, ops, count, mode, rules, allow_2q, &cand, allow_permute, alone));
     if (!have || cand.steps.size() < best.steps.size()) {
       best = std::move(cand);
       have = true;

@@ -28,3 +28,11 @@ def test_cpp_host_mirror_gpu():
     res = subprocess.run([exe, "gpu"], capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, res.stdout + res.stderr
     assert "PASSED" in res.stdout and "max|delta| vs oracle" in res.stdout
+
+
+def test_failed_wide_plan_leaves_no_scheduler_setting_behind():
+    """tests/cpp/test_plan_settings.c: after a mode 1|16 plan that fails mid-way, a mode 1 plan has a fresh process's step count"""
+    subprocess.run(["make", "-C", CPP, "-B", "test_plan_settings"], check=True, capture_output=True)
+    res = subprocess.run([os.path.join(CPP, "test_plan_settings")], capture_output=True, text=True, timeout=60)
+    assert res.returncode == 0, res.stdout + res.stderr
+    assert "PASSED" in res.stdout
