@@ -302,7 +302,9 @@ int qip_hip_jit_cache_info(uint64_t* resident, uint64_t* evicted, uint64_t* cap)
  *   "fuse"          [0]  K = 2..5: qip_hip_state_apply_ops merges consecutive gates into dense gates on <= K qubits, one sweep
  *                        each; results match the gate-by-gate path to the 1e-12 bar, not bit for bit.
  *   "tile"          [0]  1: apply_ops cuts the circuit into segments (1-qubit gates with any controls, dense 2- / 3-qubit
- *                        gates, bit swaps) whose exchanging bits fit index bits 0..5 plus five free higher positions, and applies
+ *                        gates, bit swaps, diagonal Matrix ops on 2 / 3 qubits with any controls: CZ or a ZZ phase written
+ *                        as 4x4, CCZ as 8x8 — like every diagonal item they test bits and need no tile position) whose
+ *                        exchanging bits fit index bits 0..5 plus five free higher positions, and applies
  *                        each segment in ONE sweep through an LDS-resident tile, in circuit order up to exact commutations:
  *                        IEEE-equal to the gate-by-gate path (a dense 3-qubit gate rides as the unfused register fold, i.e.
  *                        equal to its "mfma" = 0 form).  2: also hoists gates over gates they commute with (1e-12 bar).

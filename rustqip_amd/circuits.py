@@ -119,3 +119,28 @@ def c5_grover_iteration(n: int, dense_k3: bool = False) -> List[MatrixOp]:
     ops += layer(X) + mcz() + layer(X)
     ops += layer(H) + layer(X) + mcz() + layer(X) + layer(H)
     return ops
+
+
+def qaoa_ring(n: int, layers: int = 2, spelling: str = "diag", gamma: float = 0.3, beta: float = 0.4) -> List[MatrixOp]:
+    """`layers` of (a ring of n ZZ phases diag(e^-ig, e^ig, e^ig, e^-ig) on qubits (i, i + 1 mod n), n Rx gates): a QAOA cost and mixer
+    layer.  spelling: "diag" = ZZ as a 4x4 diagonal Matrix op, "cnot" = CNOT . Rz . CNOT, "stand_in" = Control([i], diag(e^-ig, e^ig)
+    on i + 1) — not the same gate, the controlled 1-qubit diagonal with the footprint of the 4x4 op (what the tile scheduler must
+    treat it like).  The one definition behind the plan tests and tools/bench_diag_items.py."""
+    ops = []
+    for layer in range(layers):
+        g = gamma * (layer + 1)
+        ez = [cmath.exp(-1j * g), 0, 0, cmath.exp(1j * g)]
+        c, s = math.cos(beta * (layer + 1)), math.sin(beta * (layer + 1))
+        for i in range(n):
+            a, b = i, (i + 1) % n
+            if spelling == "diag":
+                ops.append(make_matrix_op([a, b], np.diag([ez[0], ez[3], ez[3], ez[0]]).ravel()))
+            elif spelling == "stand_in":
+                ops.append(make_control_op([a], make_matrix_op([b], ez)))
+            elif spelling == "cnot":
+                cnot = make_control_op([a], make_matrix_op([b], X))
+                ops += [cnot, make_matrix_op([b], ez), cnot]
+            else:
+                raise ValueError(f"unknown spelling {spelling!r}")
+        ops += [make_matrix_op([i], [c, -1j * s, -1j * s, c]) for i in range(n)]
+    return ops

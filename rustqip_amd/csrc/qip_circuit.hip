@@ -217,6 +217,7 @@ template <typename T> struct SegGate {
   TileGate<T> g;  // as its literal shows it: cm_reg / cm_lane = its controls on register / lane bits
   SegCall call = SEG_OTHER;
   int j[2] = {0, 0};
+  const TileDiagSpec<T>* spec = nullptr;  // a kind-5 gate (diagonal on two / three op bits): its table and bits
 };
 
 template <typename T> struct SegWriter {
@@ -317,7 +318,7 @@ template <typename T> struct SegWriter {
   // took, 0 when no such run starts there.
   uint32_t diag_run(const std::vector<SegGate<T>>& gs, size_t k, uint32_t gi, const std::vector<uint32_t>& c) {
     size_t ke = k;
-    while (ke < gs.size() && gs[ke].g.kind == 1) ++ke;
+    while (ke < gs.size() && (gs[ke].g.kind == 1 || gs[ke].spec)) ++ke;
     if (ke - k < 3) return 0;
     std::vector<uint32_t> sets;  // element masks, in order of first appearance: F<k> is the running product of set k
     L("    {  // gates " + N(gi) + " .. " + N(gi + (ke - k) - 1) + ": one run of diagonal gates");
@@ -337,6 +338,17 @@ template <typename T> struct SegWriter {
     };
     for (size_t kj = k; kj < ke; ++kj) {
       const TileGate<T>& d = gs[kj].g;
+      if (gs[kj].spec) {  // diagonal on two / three op bits: every non-unit entry is a factor of the elements and lanes it belongs to
+        for (const TileDiagStep<T>& st : tile_diag_steps<T>(*gs[kj].spec, d, c.back())) {
+          uint32_t mask = 0;
+          for (size_t i = 0; i < c.size(); ++i)
+            if ((c[i] & st.reg_mask) == st.reg_val) mask |= 1u << i;
+          const std::string f = "A" + amp(st.f);
+          add(mask, st.lane_mask ? "tile_sel(((tb & " + N(st.lane_mask) + "u) == " + N(st.lane_val) + "u), " + f + ", A{(T)1, (T)0})" : f,
+              st.omask ? "(base & " + U(st.omask) + ") == " + U(st.oval) : "");
+        }
+        continue;
+      }
       uint32_t ok = 0;  // elements whose register-bit controls are all 1
       for (size_t i = 0; i < c.size(); ++i)
         if ((c[i] & d.cm_reg) == d.cm_reg) ok |= 1u << i;
@@ -363,6 +375,26 @@ template <typename T> struct SegWriter {
         if ((sets[si] >> i) & 1u) L("      e[" + N(i) + "] = cmul(F" + N(si) + ", e[" + N(i) + "]);");
     L("    }");
     return (uint32_t)(ke - k);
+  }
+  // A kind-5 gate: one statement per table entry that is not the unit (resolved here, as for kind 1), sub-index ascending — the
+  // elements whose register bits read the entry's sub-index (and the controls 1) take cmul(f, e), f = (1, 0) on lanes whose lane
+  // bits read otherwise, under a branch where bits outside the tile decide.  The statements select disjoint amplitudes: each one
+  // meets its own entry once, by k_diag's unfused product.  Entries other than 0 / +-1 are kernel data.  Opens the gate's block
+  // (the caller closes it with end_gate); returns true when a statement sits under a block-uniform branch.
+  bool diag_item(uint32_t gi, const TileGate<T>& g, const TileDiagSpec<T>& sp, const std::vector<uint32_t>& c) {
+    L("    {  // gate " + N(gi) + ": diagonal on " + N(sp.k) + " bits");
+    bool uniform = false;
+    for (const TileDiagStep<T>& st : tile_diag_steps<T>(sp, g, c.back())) {
+      std::string body = "A f = " + amp(st.f) + "; ";
+      if (st.lane_mask)
+        body += "{ const bool lane_ok = (tb & " + N(st.lane_mask) + "u) == " + N(st.lane_val) + "u; f.x = lane_ok ? f.x : (T)1; f.y = lane_ok ? f.y : (T)0; } ";
+      for (size_t i = 0; i < c.size(); ++i)
+        if ((c[i] & st.reg_mask) == st.reg_val) body += "e[" + N(i) + "] = cmul(f, e[" + N(i) + "]); ";
+      if (st.omask) L("      if ((base & " + U(st.omask) + ") == " + U(st.oval) + ") { QIP_KEEP_BRANCH(); " + body + "}");
+      else L("      { " + body + "}");
+      uniform = uniform || st.omask != 0;
+    }
+    return uniform;
   }
   void gate_literal(uint32_t gi, const TileGate<T>& g) {
     L("    {  // gate " + N(gi));
@@ -490,6 +522,7 @@ static std::string tile_jit_source(const TileSegmentPlan<T>& plan, const Ins& in
       else if (op >= TOP_DENSE0 && op <= TOP_DENSE2) r = {g, SEG_DENSE, {(int)(op - TOP_DENSE0)}};
       else if (op >= TOP_DENSE_LANE0 && op <= TOP_DENSE_LANE2) r = {g, SEG_DENSE_LANE, {(int)(op - TOP_DENSE_LANE0)}};
       else if (op >= TOP_SWAP_01 && op <= TOP_SWAP_12) r = {g, SEG_SWAP, {sa[op - TOP_SWAP_01], sb[op - TOP_SWAP_01]}};
+      if (g.kind == (uint32_t)kTileKindDiagK) r.spec = &plan.diags[g.nz];
       gs.push_back(r);
     }
     for (size_t k = 0; k < gs.size(); ++k) {
@@ -500,6 +533,11 @@ static std::string tile_jit_source(const TileSegmentPlan<T>& plan, const Ins& in
           continue;
         }
       const TileGate<T>& g = gs[k].g;
+      if (gs[k].spec) {
+        w.diag_item(gi, g, *gs[k].spec, c);
+        w.end_gate();
+        continue;
+      }
       w.gate_literal(gi, g);
       std::string call = SegWriter<T>::gate_call(gs[k]);
       static const int ja[6] = {0, 0, 1, 1, 2, 2}, jb[6] = {1, 2, 0, 2, 0, 1};
@@ -659,6 +697,7 @@ static std::string wide_jit_source(const WidePlan<T>& plan, const Ins& ins, bool
       else if (g.kind == 1) r.call = g.b0 == kTileOutside && !g.cm_lane ? SEG_DIAG_UNIFORM : g.cm_lane ? SEG_DIAG_LANE_CTL : SEG_DIAG_LANE;
       else if (g.kind == 0) r = {g, g.cm_lane ? SEG_DENSE_LANE : SEG_DENSE, {jof(g.b0)}};
       else if (g.kind == 2) r = {g, SEG_SWAP, {jof(g.b0), jof(g.b1)}};
+      if (g.kind == (uint32_t)kTileKindDiagK) r.spec = &plan.diags[g.nz];
       gs.push_back(r);
     }
     for (size_t k = 0; k < gs.size(); ++k) {
@@ -669,6 +708,15 @@ static std::string wide_jit_source(const WidePlan<T>& plan, const Ins& ins, bool
           continue;
         }
       const TileGate<T>& g = gs[k].g;
+      if (gs[k].spec) {
+        if (w.diag_item(gi, g, *gs[k].spec, c) && pin) {
+          std::string pl = "     ";
+          for (int i = 0; i < 32; ++i) pl += " asm volatile(\"\" : \"+v\"(e[" + N(i) + "].x), \"+v\"(e[" + N(i) + "].y));";
+          L(pl);
+        }
+        w.end_gate();
+        continue;
+      }
       w.gate_literal(gi, g);
       std::string call = SegWriter<T>::gate_call(gs[k]);
       const amp_t<T>* M = g.kind >= 3 ? plan.mats.data() + 16 * g.nz : nullptr;  // (the matrix of a dense 2- or 3-qubit gate)
@@ -841,8 +889,10 @@ static int launch_tile_segment(qip_hip_state* s, const BatchRun& run, const std:
   // r5: the interpreter kernel takes runs of diagonal gates as one loop over TileDiagItem steps (tile_merge_diag_runs: the same
   // products in the same order, without the per-gate decoding); the plan itself stays what the generators and the CPU replay read
   TileInterpPlan<T> interp;
-  const bool use_runs = g_tile_diag_runs && s->tile_passes && !run.tile_jit;
-  if (use_runs) tile_merge_diag_runs<T>(plan, &interp);
+  // (a kind-5 gate has no other form in the interpreter: with the option off, the runs that hold one are still made)
+  if (!s->tile_passes && !plan.diags.empty()) return fail(QIP_ERR_INVALID, "internal: a multi-qubit diagonal item in a k_tile_gates segment");
+  const bool use_runs = (g_tile_diag_runs || !plan.diags.empty()) && s->tile_passes && !run.tile_jit;
+  if (use_runs) tile_merge_diag_runs<T>(plan, &interp, g_tile_diag_runs ? 2u : ~0u);
   const bool has_runs = use_runs && interp.runs > 0;
   std::vector<TileGate<T>>& gates = has_runs ? interp.gates : plan.gates;
   std::vector<amp_t<T>>& mats = plan.mats;
@@ -1200,6 +1250,14 @@ static int apply_ops_tiled(qip_hip_state* s, const qip_op* ops_in, uint64_t coun
         mix(it.d_mask);
         for (uint32_t c : it.cpos) mix(0x100u + c);
         mix(it.t0 | (uint64_t)it.t1 << 8 | (uint64_t)it.t2 << 16);
+        // its width and which entries are the unit.  Like the other kinds' part of the fingerprint this is not everything a source
+        // depends on (a component that becomes exactly 0 / +-1 turns from kernel data into a literal): a plan remembered as warm only
+        // skips the pre-compilation pass, a segment that is not resident is still compiled when it is launched
+        if (it.kind == kTileKindDiagK) {
+          uint64_t units = 0;
+          for (uint32_t e = 0; e < (1u << it.dk); ++e) units |= (uint64_t)(it.mat[2 * e] == 1.0 && it.mat[2 * e + 1] == 0.0) << e;
+          mix(0x5D000000ull | (uint64_t)it.dk << 16 | units);
+        }
       }
     }
     const JitPlanMemo memo = jit_plan_query(fp);

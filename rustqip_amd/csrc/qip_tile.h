@@ -8,13 +8,14 @@ struct TileItem {
   // every matrix entry is in {0, +-1, +-i}: the gate moves / negates / rotates amplitudes by 90 degrees without
   // any rounding, so it commutes with gates on other qubits EXACTLY (IEEE ==), not just mathematically
   bool exact = false;
-  int kind = 0;                 // TileGate kind
+  int kind = 0;                 // TileGate kind, or kTileKindDiagK (host-side only, see below)
   std::vector<uint32_t> pos;    // every involved bit position
   uint32_t t0 = 0, t1 = 0, t2 = 0;  // target position(s)
   std::vector<uint32_t> cpos;
   double m[8] = {0};
   uint32_t nz = 0;
-  std::vector<double> mat;  // kind 3 / 4: 4x4 / 8x8 row-major as re,im pairs, sub-index MSB = t0
+  std::vector<double> mat;  // kind 3 / 4: 4x4 / 8x8 row-major as re,im pairs, sub-index MSB = t0; kind 5: the 2^dk diagonal entries
+  uint32_t dk = 0;          // kind 5: number of op bits (2 or 3): t0 (sub-index MSB), t1[, t2]
   // how the gate acts on each of its bits: `nd_mask` = it exchanges amplitudes across the bit (dense target, swap
   // bits), `d_mask` = it only tests the bit (controls, diagonal targets).  Two gates commute when on every bit
   // they share both only test it.  Ops that are not tileable count every bit as exchanged.
@@ -23,6 +24,60 @@ struct TileItem {
   // permutation of the index bits (launch_permute)
   std::vector<std::pair<uint32_t, uint32_t>> swap_pairs;
 };
+// Kind 5: a diagonal gate on two or three op bits (any controls), `mat` = its table.  Like kind 1 it exchanges nothing, so none of
+// its bits needs a tile position.  The kernels have no descriptor form for it: a segment plan keeps its table and bits in a
+// TileDiagSpec beside the gate list (TileGate::nz = the index, TileGate::op = kTopDiagItem), and every consumer expands it against
+// the pass it sits in into one step per non-unit entry (tile_diag_steps) — TileDiagItem steps of a TOP_DIAG_RUN for the
+// interpreter kernel, straight-line products in generated segments.
+constexpr int kTileKindDiagK = 5;
+constexpr uint32_t kTopDiagItem = (uint32_t)TOP_DIAG_RUN + 1u;  // never reaches a kernel (tile_merge_diag_runs replaces it)
+static inline bool tile_item_is_diag(const TileItem& it) { return it.kind == 1 || it.kind == kTileKindDiagK; }
+// the kinds k_tile_gates (tile_passes = 0) has no form for: such an item is a step of its own there, run by the op's own kernel
+static inline bool tile_item_needs_passes(const TileItem& it) { return it.kind == 3 || it.kind == 4 || it.kind == kTileKindDiagK; }
+template <typename T> struct TileDiagSpec {
+  uint32_t k;       // op bits
+  uint32_t bit[3];  // tile-index bit of op bit j (j = 0: sub-index MSB), kTileOutside when the position is outside the tile
+  uint32_t pos[3];  // amplitude-index position of op bit j
+  amp_t<T> f[8];    // the table
+};
+// one step: the amplitudes whose register bits, lane bits and block base read the given values are multiplied by f (the gate's
+// controls are part of the conditions, as ones)
+template <typename T> struct TileDiagStep {
+  amp_t<T> f;
+  uint32_t lane_mask, lane_val, reg_mask, reg_val;
+  uint64_t omask, oval;
+};
+// The steps of a kind-5 gate where `regmask` are the tile bits a lane holds in registers: one per table entry that is not the
+// unit, sub-index ascending.  The steps select disjoint amplitudes, so each amplitude meets its own entry once.
+template <typename T>
+static inline std::vector<TileDiagStep<T>> tile_diag_steps(const TileDiagSpec<T>& sp, const TileGate<T>& g, uint32_t regmask) {
+  std::vector<TileDiagStep<T>> steps;
+  for (uint32_t sub = 0; sub < (1u << sp.k); ++sub) {
+    const amp_t<T> f = sp.f[sub];
+    if (f.x == (T)1 && f.y == (T)0) continue;
+    TileDiagStep<T> st;
+    st.f = f;
+    st.reg_mask = st.reg_val = g.cmask & regmask;
+    st.lane_mask = st.lane_val = g.cmask & ~regmask;
+    st.omask = st.oval = g.omask;
+    for (uint32_t j = 0; j < sp.k; ++j) {
+      const uint32_t v = (sub >> (sp.k - 1u - j)) & 1u;
+      if (sp.bit[j] == kTileOutside) {
+        st.omask |= 1ull << sp.pos[j];
+        st.oval |= (uint64_t)v << sp.pos[j];
+      } else if ((regmask >> sp.bit[j]) & 1u) {
+        st.reg_mask |= 1u << sp.bit[j];
+        st.reg_val |= v << sp.bit[j];
+      } else {
+        st.lane_mask |= 1u << sp.bit[j];
+        st.lane_val |= v << sp.bit[j];
+      }
+    }
+    steps.push_back(st);
+  }
+  return steps;
+}
+
 // The positions a tileable item exchanges amplitudes across — a dense target, both swap bits; a diagonal gate has none — which
 // are the positions that must be tile bits (controls and diagonal targets may stay outside).  Returns how many; the entries of
 // `out` behind them mean nothing.
@@ -41,13 +96,15 @@ template <typename T> struct TileSegmentPlan {
   std::vector<uint32_t> high;  // amplitude-index position of tile bit 6 + j
   std::vector<TileGate<T>> gates;
   std::vector<amp_t<T>> mats;  // 4x4 matrices of the dense 2-qubit gates (kind 3), 16 entries each
+  std::vector<TileDiagSpec<T>> diags;  // tables and bits of the kind-5 gates (TileGate::nz)
   TilePassDesc pd;             // passes (only when `passes`)
   uint32_t p5 = 5;             // amplitude-index position of tile bit 5
   std::vector<uint32_t> order; // gates[i] is the segment's order[i]-th op (build_tile_segment may reorder inside the segment)
 };
 
 // r5: what the INTERPRETER kernel (k_tile_passes) is handed for a segment: the plan's gate list with every run of >= 2
-// consecutive diagonal gates of a pass replaced by one TOP_DIAG_RUN entry + its TileDiagItem steps (qip_kernels.h).  The plan
+// consecutive diagonal gates of a pass replaced by one TOP_DIAG_RUN entry + its TileDiagItem steps (qip_kernels.h); a kind-5 gate
+// is always part of a run, whatever `min_run` (a run of its own if it has no diagonal neighbour).  The plan
 // itself — what the run-time generators, the CPU replay and the one-op sweeps consume — is unchanged.
 template <typename T> struct TileInterpPlan {
   std::vector<TileGate<T>> gates;
@@ -131,6 +188,7 @@ template <typename T> struct WidePlan {
   uint32_t p5 = 5;
   std::vector<TileGate<T>> gates;  // b0 / b1 / tpos_out / cmask in the 13-bit tile-index space; op, cm_reg, cm_lane unused
   std::vector<amp_t<T>> mats;
+  std::vector<TileDiagSpec<T>> diags;  // kind 5, as in TileSegmentPlan
   std::vector<WidePass> passes;    // passes.back() may hold no gate: the way back to the load arrangement
   std::vector<uint32_t> order;
 };

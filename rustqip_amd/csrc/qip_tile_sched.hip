@@ -59,6 +59,34 @@ int classify_tile_item(int dtype, uint32_t n, const qip_op* op, TileItem* it) {
     for (int e = 0; e < 4; ++e) it->m[e] = p.table[e];
     it->tileable = true;
     it->exact = unit_axis(p.table[0], p.table[1]) && unit_axis(p.table[2], p.table[3]);
+  } else if ((p.cls == KC_PHASE || p.cls == KC_DIAG) && (k == 2 || k == 3)) {
+    const uint32_t side = 1u << k;
+    if (p.cls == KC_PHASE && p.phase_ones == (uint64_t)side - 1u) {
+      // the one entry sits where every op bit reads 1: a phase on the last op bit, the other op bits are controls
+      it->kind = 1;
+      it->t0 = p.opos[k - 1];
+      for (uint32_t j = 0; j + 1 < k; ++j) it->cpos.push_back(p.opos[j]);
+      it->m[0] = 1.0;
+      it->m[1] = 0.0;
+      it->m[2] = p.phase[0];
+      it->m[3] = p.phase[1];
+      it->exact = unit_axis(p.phase[0], p.phase[1]);
+    } else {
+      it->kind = kTileKindDiagK;  // diagonal on two / three op bits: the table travels with the item
+      it->dk = k;
+      it->t0 = p.opos[0];
+      it->t1 = p.opos[1];
+      it->t2 = k == 3 ? p.opos[2] : 0;
+      it->mat.assign(2 * side, 0.0);
+      for (uint32_t e = 0; e < side; ++e) {
+        const bool own = p.cls == KC_DIAG || e == (uint32_t)p.phase_ones;
+        it->mat[2 * e] = !own ? 1.0 : p.cls == KC_DIAG ? p.table[2 * e] : p.phase[0];
+        it->mat[2 * e + 1] = !own ? 0.0 : p.cls == KC_DIAG ? p.table[2 * e + 1] : p.phase[1];
+      }
+      it->exact = true;
+      for (uint32_t e = 0; e < side; ++e) it->exact = it->exact && unit_axis(it->mat[2 * e], it->mat[2 * e + 1]);
+    }
+    it->tileable = true;
   } else if (p.cls == KC_SWAP_BITS && k == 2) {
     it->kind = 2;
     it->t0 = std::min(p.opos[0], p.opos[1]);
@@ -83,8 +111,10 @@ int classify_tile_item(int dtype, uint32_t n, const qip_op* op, TileItem* it) {
   }
   it->nd_mask = it->d_mask = 0;
   if (it->tileable) {
-    for (uint32_t c : p.cpos) it->d_mask |= 1ull << c;
+    for (uint32_t c : it->cpos) it->d_mask |= 1ull << c;
     if (it->kind == 1) it->d_mask |= 1ull << it->t0;
+    if (it->kind == kTileKindDiagK)
+      for (uint32_t t : p.opos) it->d_mask |= 1ull << t;
     uint32_t ex[3];
     for (int e = 0, ne = tile_exch(*it, ex); e < ne; ++e) it->nd_mask |= 1ull << ex[e];
   } else {
@@ -172,6 +202,24 @@ static std::vector<uint32_t> seg_exch_uses(const std::vector<const TileItem*>& s
     for (int e = 0, ne = tile_exch(*it, ex); e < ne; ++e) uses[ex[e]] += 1;
   }
   return uses;
+}
+
+// a kind-5 item as its gate descriptor (no target bit of its own: b0 reads "outside") and its entry in the plan's `diags`
+template <typename T, typename TileBit>
+static void seg_diag_item(const TileItem& it, TileBit tile_bit, TileGate<T>* g, std::vector<TileDiagSpec<T>>* diags) {
+  TileDiagSpec<T> sp;
+  memset(&sp, 0, sizeof sp);
+  sp.k = it.dk;
+  const uint32_t t[3] = {it.t0, it.t1, it.t2};
+  for (uint32_t j = 0; j < sp.k; ++j) {
+    sp.pos[j] = t[j];
+    sp.bit[j] = tile_bit(t[j]);
+  }
+  for (uint32_t e = 0; e < (1u << sp.k); ++e) sp.f[e] = mk<T>(it.mat[2 * e], it.mat[2 * e + 1]);
+  g->b0 = kTileOutside;
+  g->b1 = 0;
+  g->nz = (uint32_t)diags->size();
+  diags->push_back(sp);
 }
 
 // The order the gates of a segment (at most 256) must keep among themselves, under the commutation relation the scheduler itself
@@ -366,6 +414,7 @@ int build_tile_segment(uint32_t n, bool passes, const std::vector<const TileItem
   std::vector<amp_t<T>>& mats = out->mats;
   gates.assign(seg.size(), TileGate<T>());
   mats.clear();
+  out->diags.clear();
   for (size_t i = 0; i < seg.size(); ++i) {
     const TileItem& it = *seg[i];
     TileGate<T>& g = gates[i];
@@ -387,6 +436,7 @@ int build_tile_segment(uint32_t n, bool passes, const std::vector<const TileItem
       else g.cmask |= 1u << tb;
     }
     if (it.kind != 3 && it.kind != 4) g.nz = it.nz;
+    if (it.kind == kTileKindDiagK) seg_diag_item<T>(it, tile_bit, &g, &out->diags);
     if (it.kind == 0) {
       for (int e = 0; e < 4; ++e) g.m[e] = mk<T>(it.m[2 * e], it.m[2 * e + 1]);
       if (passes) {  // flop-saving flags (k_tile_passes only; k_tile_gates reads b1 = 0)
@@ -422,9 +472,15 @@ int build_tile_segment(uint32_t n, bool passes, const std::vector<const TileItem
       int score[kTileBits] = {0};
       for (uint32_t gi = first; gi < end; ++gi) {
         const TileGate<T>& g = gates[gi];
-        if (g.kind != 1) continue;
+        if (g.kind != 1 && g.kind != (uint32_t)kTileKindDiagK) continue;
         for (int t = 0; t < kTileBits; ++t)
           if ((g.cmask >> t) & 1u) score[t] += 1;
+        if (g.kind == (uint32_t)kTileKindDiagK) {  // every op bit on a pass bit is a wave-uniform element test instead of a per-lane select
+          const TileDiagSpec<T>& sp = out->diags[g.nz];
+          for (uint32_t j = 0; j < sp.k; ++j)
+            if (sp.bit[j] != kTileOutside) score[sp.bit[j]] += 1;
+          continue;
+        }
         const bool unit0 = g.m[0].x == (T)1 && g.m[0].y == (T)0, unit1 = g.m[1].x == (T)1 && g.m[1].y == (T)0;
         if (g.b0 != kTileOutside && (unit0 || unit1)) score[g.b0] += 1;
       }
@@ -510,6 +566,8 @@ int build_tile_segment(uint32_t n, bool passes, const std::vector<const TileItem
                                                {TOP_DENSE2Q_10, 0, TOP_DENSE2Q_12},
                                                {TOP_DENSE2Q_20, TOP_DENSE2Q_21, 0}};
           g.op = table[ja][jb];
+        } else if (g.kind == (uint32_t)kTileKindDiagK) {
+          g.op = kTopDiagItem;
         } else {
           const uint32_t ja = jof(g.b0), jb = jof(g.b1);  // b0 < b1 and pass bits ascend, so ja < jb
           g.op = ja == 0 ? (jb == 1 ? TOP_SWAP_01 : TOP_SWAP_02) : TOP_SWAP_12;
@@ -533,6 +591,9 @@ int build_tile_segment(uint32_t n, bool passes, const std::vector<const TileItem
 //            target outside both halves are kept, units too (the op multiplies by whatever m[bit] is)
 //   REG J    (target = pass bit J): per non-unit half h, F = m[h] (or (1, 0) where a lane-bit control is 0) on the elements with
 //            bit J = h and the pass-bit controls 1                     -> {f1 = m[h], reg_mask += bit J, reg_val += h << J}
+// A diagonal gate on two / three op bits (kind 5, qip_tile.h) has no code path of its own: it is one step per table entry that is
+// not the unit (tile_diag_steps) — the entry's sub-index spelt as VALUES of the op bits in the lane, pass-bit and outside
+// conditions, the controls as ones — and therefore always part of a run, whatever `min_run`.
 // ---------------------------------------------------------------------------------------
 int64_t g_tile_diag_runs = 1;
 template <typename T>
@@ -542,7 +603,8 @@ void tile_merge_diag_runs(const TileSegmentPlan<T>& plan, TileInterpPlan<T>* out
   out->pd = plan.pd;
   out->runs = out->gates_in_runs = 0;
   auto unit = [](const amp_t<T>& a) { return a.x == (T)1 && a.y == (T)0; };
-  auto is_diag = [](const TileGate<T>& g) { return g.kind == 1 && g.op <= (uint32_t)TOP_DIAG_REG2; };
+  auto is_item = [](const TileGate<T>& g) { return g.kind == (uint32_t)kTileKindDiagK; };
+  auto is_diag = [&](const TileGate<T>& g) { return (g.kind == 1 && g.op <= (uint32_t)TOP_DIAG_REG2) || is_item(g); };
   for (uint32_t pi = 0; pi < plan.pd.npasses; ++pi) {
     const TilePass& ps = plan.pd.pass[pi];
     TilePass& po = out->pd.pass[pi];
@@ -551,8 +613,9 @@ void tile_merge_diag_runs(const TileSegmentPlan<T>& plan, TileInterpPlan<T>* out
     const uint32_t gend = ps.first + ps.count;
     while (gi < gend) {
       uint32_t ge = gi;
-      while (ge < gend && is_diag(plan.gates[ge])) ++ge;
-      if (ge - gi < min_run) {  // not a run: the gate as it is (and the non-diagonal gate that ended the scan, if any)
+      bool has_item = false;  // (a kind-5 gate has no code path of its own: always a run)
+      for (; ge < gend && is_diag(plan.gates[ge]); ++ge) has_item = has_item || is_item(plan.gates[ge]);
+      if (ge - gi < min_run && !has_item) {  // not a run: the gate as it is (and the non-diagonal gate that ended the scan, if any)
         const uint32_t upto = std::max(ge, gi + 1);
         for (; gi < upto && gi < gend; ++gi) out->gates.push_back(plan.gates[gi]);
         continue;
@@ -587,7 +650,11 @@ void tile_merge_diag_runs(const TileSegmentPlan<T>& plan, TileInterpPlan<T>* out
       for (; gi < ge; ++gi) {
         const TileGate<T>& g = plan.gates[gi];
         const bool outside = g.b0 == kTileOutside;
-        if (g.op == TOP_DIAG_UNIFORM || (outside && (g.op == TOP_DIAG_LANE || g.op == TOP_DIAG_LANE_CTL))) {
+        if (is_item(g)) {  // one step per non-unit entry: each amplitude meets its own entry once, by the products of every step
+          const uint32_t passmask = (1u << ps.pb[0]) | (1u << ps.pb[1]) | (1u << ps.pb[2]);
+          for (const TileDiagStep<T>& st : tile_diag_steps<T>(plan.diags[g.nz], g, passmask))
+            push(st.f, st.f, st.lane_mask, st.lane_val, st.reg_mask, st.reg_val, st.omask, st.oval, 0u);
+        } else if (g.op == TOP_DIAG_UNIFORM || (outside && (g.op == TOP_DIAG_LANE || g.op == TOP_DIAG_LANE_CTL))) {
           for (int h = 0; h < 2; ++h) {
             if (g.op == TOP_DIAG_UNIFORM && unit(g.m[h])) continue;
             push(g.m[h], g.m[h], g.cm_lane, g.cm_lane, g.cm_reg, g.cm_reg, g.omask | (1ull << g.tpos_out), g.omask | ((uint64_t)h << g.tpos_out), 0u);
@@ -628,8 +695,9 @@ template void tile_merge_diag_runs<float>(const TileSegmentPlan<float>&, TileInt
 //     the same two products as X followed by M, added in the other order: bit-equal.  M.X = 1 (M was a second X in disguise: never
 //     here, X toggles) leaves the list too;
 //   * a diagonal 1-qubit gate on t in P with no control in P: its two entries swapped, t stays pending;
-//   * anything else that touches a pending bit (a control on it, a controlled dense gate, swaps, dense 2- / 3-qubit items): the
-//     X items of those bits come back in front of it, as they were.
+//   * anything else that touches a pending bit (a control on it, a controlled dense gate, swaps, dense 2- / 3-qubit items, a
+//     diagonal item on two / three op bits — its table is not permuted): the X items of those bits come back in front of it, as
+//     they were.
 // What is pending at the end is the sweep's flip.  Exactness under tile = 1's ordering rule: the rewritten list in its own order is
 // bit-equal to the segment in its order, and its items commute exactly where the originals did.
 // ---------------------------------------------------------------------------------------
@@ -931,6 +999,7 @@ int build_wide_segment(uint32_t n, const std::vector<const TileItem*>& seg_in, s
   std::vector<amp_t<T>>& mats = out->mats;
   gates.assign(seg.size(), TileGate<T>());
   mats.clear();
+  out->diags.clear();
   out->order.resize(seg.size());
   for (size_t i = 0; i < seg.size(); ++i) {
     out->order[i] = (uint32_t)(std::find(seg_in.begin(), seg_in.end(), seg[i]) - seg_in.begin());
@@ -953,6 +1022,7 @@ int build_wide_segment(uint32_t n, const std::vector<const TileItem*>& seg_in, s
       else g.cmask |= 1u << tb;
     }
     if (it.kind != 3 && it.kind != 4) g.nz = it.nz;
+    if (it.kind == kTileKindDiagK) seg_diag_item<T>(it, tile_bit, &g, &out->diags);
     if (it.kind == 0) {
       for (int e = 0; e < 4; ++e) g.m[e] = mk<T>(it.m[2 * e], it.m[2 * e + 1]);
       const bool real = it.m[1] == 0 && it.m[3] == 0 && it.m[5] == 0 && it.m[7] == 0;
@@ -962,7 +1032,7 @@ int build_wide_segment(uint32_t n, const std::vector<const TileItem*>& seg_in, s
       g.m[0] = mk<T>(it.m[0], it.m[1]);
       g.m[1] = mk<T>(it.m[2], it.m[3]);
     }
-    if ((it.kind != 1 && g.b0 == kTileOutside) || (it.kind >= 2 && g.b1 == kTileOutside) || (it.kind == 4 && g.tpos_out == kTileOutside))
+    if ((!tile_item_is_diag(it) && g.b0 == kTileOutside) || (it.kind >= 2 && g.b1 == kTileOutside) || (it.kind == 4 && g.tpos_out == kTileOutside))
       return fail(QIP_ERR_INVALID, "internal: an exchange target outside the wide tile");
   }
   // LDS layout of one transposition (see WidePass::bufpos): thread-id bits 0..3 of the writing arrangement land on buffer bits
@@ -1044,7 +1114,7 @@ int build_wide_segment(uint32_t n, const std::vector<const TileItem*>& seg_in, s
   }
   if (getenv("QIP_WIDE_DEBUG")) {
     size_t exg = 0;
-    for (const auto& g : gates) exg += g.kind != 1;
+    for (const auto& g : gates) exg += g.kind != 1 && g.kind != (uint32_t)kTileKindDiagK;
     fprintf(stderr, "[wide] %zu gates (%zu exchanging), %zu transpositions\n", gates.size(), exg, passes.size() - 1);
   }
   return QIP_OK;
@@ -1108,7 +1178,7 @@ static int seg_scan(const SegScan& c, uint64_t head, const std::vector<uint32_t>
       continue;
     }
     const bool commutes = !(it.nd_mask & (blocked_nd | blocked_d)) && !(it.d_mask & blocked_nd);
-    bool fits = it.tileable && commutes && (c.reorder || it.exact || !skipped_inexact) && (it.kind == 1 || exch_gates < c.max_exch);
+    bool fits = it.tileable && commutes && (c.reorder || it.exact || !skipped_inexact) && (tile_item_is_diag(it) || exch_gates < c.max_exch);
     uint32_t claim[3], nclaim = 0;  // the positions the tile has to claim for it, in the order the item names them
     uint64_t with = tile;
     if (fits) {
@@ -1125,7 +1195,7 @@ static int seg_scan(const SegScan& c, uint64_t head, const std::vector<uint32_t>
       room -= nclaim;
       QCHK(join(i, claim, nclaim));
       joined += 1;
-      exch_gates += it.kind != 1;
+      exch_gates += !tile_item_is_diag(it);
     } else {
       blocked_nd |= it.nd_mask;
       blocked_d |= it.d_mask;
@@ -1144,7 +1214,7 @@ static double seg_dry_run(const SegScan& c, uint64_t head, const std::vector<uin
   seg_scan(
       c, head, c.relabel ? trial : phys, seg_tile_mask(c.p5, H), 0,
       [&](uint64_t i, const uint32_t*, uint32_t) {
-        w += c.L[i].kind != 1 ? 1.0 : (c.rules.claim == 3 ? 0.5 : 0.125);
+        w += !tile_item_is_diag(c.L[i]) ? 1.0 : (c.rules.claim == 3 ? 0.5 : 0.125);
         return (int)QIP_OK;
       },
       [&](uint64_t i) {
@@ -1182,7 +1252,8 @@ static std::vector<uint32_t> seg_choose_high(const SegScan& c, uint64_t head, co
   return H;
 }
 
-// the caller's ops as tile items (2- / 3-qubit dense items only where the kernel that will run them has the form)
+// the caller's ops as tile items (dense 2- / 3-qubit items and diagonal items on two / three op bits only where the kernel that
+// will run them has the form: `allow_2q`, see tile_item_needs_passes)
 static int classify_tile_items(int dtype, uint32_t n, const qip_op* ops, uint64_t count, bool allow_2q, std::vector<TileItem>* items) {
   items->assign(count, TileItem());
   for (uint64_t i = 0; i < count; ++i) {
@@ -1191,7 +1262,7 @@ static int classify_tile_items(int dtype, uint32_t n, const qip_op* ops, uint64_
       std::string msg = g_last_error;
       return fail(rc, "op %llu: %s", (unsigned long long)i, msg.c_str());
     }
-    if ((*items)[i].kind >= 3 && !allow_2q) (*items)[i].tileable = false;  // k_tile_gates has no 2- / 3-qubit form
+    if (!allow_2q && tile_item_needs_passes((*items)[i])) (*items)[i].tileable = false;
   }
   return QIP_OK;
 }
@@ -1302,7 +1373,7 @@ static int schedule_tiles_relabel(int dtype, uint32_t n, const qip_op* ops, uint
     out->origin.push_back(origin);
     out->items.emplace_back();
     int rc = classify_tile_item(dtype, n, &out->owned.back(), &out->items.back());
-    if (rc == QIP_OK && out->items.back().kind >= 3 && !allow_2q) out->items.back().tileable = false;
+    if (rc == QIP_OK && !allow_2q && tile_item_needs_passes(out->items.back())) out->items.back().tileable = false;
     return rc;
   };
   // the caller's op i under the labels in force now: same descriptor, qubit indices mapped through `phys`
@@ -1539,6 +1610,22 @@ static int tile_plan_json(int dtype, uint32_t n, const qip_op* ops, uint64_t cou
     }
     js += "]";
   }
+  // the kind-5 gates of a segment (gate "nz" = index): op bits (tile bit, position; MSB first) and table.  Absent when there is none
+  auto diag_json = [&](const std::vector<TileDiagSpec<T>>& diags) {
+    if (diags.empty()) return;
+    js += ",\"diag\":[";
+    for (size_t k = 0; k < diags.size(); ++k) {
+      const TileDiagSpec<T>& sp = diags[k];
+      js += std::string(k ? "," : "") + "{\"bits\":[";
+      for (uint32_t j = 0; j < sp.k; ++j) js += (j ? "," : "") + std::to_string(sp.bit[j]);
+      js += "],\"pos\":[";
+      for (uint32_t j = 0; j < sp.k; ++j) js += (j ? "," : "") + std::to_string(sp.pos[j]);
+      js += "],\"f\":[";
+      for (uint32_t e = 0; e < (1u << sp.k); ++e) js += std::string(e ? "," : "") + "[" + num((double)sp.f[e].x) + "," + num((double)sp.f[e].y) + "]";
+      js += "]}";
+    }
+    js += "]";
+  };
   // one segment plan: the tile's positions, the order, the passes, the gate descriptors and matrices (+ the interpreter's runs)
   auto emit_segment = [&](const TileSegmentPlan<T>& plan, bool with_interp) {
     js += ",\"low\":[0,1,2,3,4," + std::to_string(plan.p5) + "],\"high\":[";
@@ -1572,6 +1659,7 @@ static int tile_plan_json(int dtype, uint32_t n, const qip_op* ops, uint64_t cou
     for (size_t e = 0; e < plan.mats.size(); ++e)
       js += std::string(e ? "," : "") + "[" + num((double)plan.mats[e].x) + "," + num((double)plan.mats[e].y) + "]";
     js += "]";
+    diag_json(plan.diags);
     if (with_interp) {  // r5: what the interpreter kernel is handed instead — runs of diagonal gates as TileDiagItem steps
       TileInterpPlan<T> ip;
       tile_merge_diag_runs<T>(plan, &ip);
@@ -1653,6 +1741,7 @@ static int tile_plan_json(int dtype, uint32_t n, const qip_op* ops, uint64_t cou
       for (size_t e = 0; e < plan.mats.size(); ++e)
         js += std::string(e ? "," : "") + "[" + num((double)plan.mats[e].x) + "," + num((double)plan.mats[e].y) + "]";
       js += "]";
+      diag_json(plan.diags);
     } else if (st.ops.size() > 1) {
       std::vector<const TileItem*> seg;
       for (uint64_t i : st.ops) seg.push_back(&items[i]);

@@ -320,6 +320,10 @@ TILE_PLAN_INTERP, TILE_PLAN_ABSORB_X = 1024, 4096  # mode bits of debug_tile_pla
 # "b1" of a dense 1-qubit item (kind 0) in the "absorb" lists of debug_tile_plan, beside 1 = real entries and 2 = X (csrc/qip_kernels.h
 # TileGate, kTileSignRows / kTileSignNeg0 / kTileSignNeg1): row 1 is row 0 up to one sign per column; column 0 / 1 negated
 TILE_SIGN_ROWS, TILE_SIGN_NEG0, TILE_SIGN_NEG1 = 4, 8, 16
+# "kind" of a diagonal gate on two / three op bits in the gate lists of debug_tile_plan (csrc/qip_tile.h kTileKindDiagK): its "nz"
+# indexes the segment's "diag" list ({"bits": tile bit per op bit, MSB first, 0xffffffff = outside the tile; "pos": amplitude-index
+# positions; "f": the table}); in the "interp" lists it is always steps of a diagonal run
+TILE_KIND_DIAG_K = 5
 
 
 def debug_tile_plan(n: int, ops, mode: int = 1, dtype: int = _ffi.QIP_C64) -> dict:

@@ -11,9 +11,12 @@
 //   V3  persistent blocks, next tile DMA-ed (global_load_lds) into a second LDS slot during the passes: 2 blocks per CU
 //   V4  persistent blocks, next tile's loads held in registers during the passes: 4 blocks per CU
 //   V5  persistent blocks without prefetch, 5 per CU (control for V3 / V4)
+//   tools/tune_tile [n] [reps] diag8 : diagonal gates on three op bits with dense tables, host expansion into diagonal-run steps
+//       against a table lookup (k_diag8, profiles/diag_items.md)
 #include <hip/hip_runtime.h>
 #include "../rustqip_amd/csrc/qip_kernels.h"
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -407,6 +410,88 @@ __global__ __launch_bounds__(512, BPC) void k_v13w(A* __restrict__ st, Hp7 hp, A
   for (int u = 0; u < 16; ++u) stg<true>(st + (w | off(u)) + lane_off, x[u]);
 }
 
+// "diag8" study (profiles/diag_items.md): D diagonal gates on THREE op bits — one outside the tile (amplitude position `opos`), one
+// on a lane bit (tile bit 3), one on a pass bit (tile bit 8 = bit 0 of the element index) — with dense 8-entry tables, in the one
+// pass of a light sweep, in the two forms the interpreter could give such an item:
+//   FORM 0  host expansion: 8 TileDiagItem steps per gate, the loop of k_tile_passes' TOP_DIAG_RUN copied statement by statement
+//           (block-uniform test of the outside bit, lane condition folded into the factor, one emask bit per element)
+//   FORM 1  table lookup: per gate one descriptor (positions at run time, as a product kernel would take them) and its table in
+//           global memory; sub-index = outside part | lane part | the element's host-resolved part, factor = table[sub] per element
+// Either way every amplitude is multiplied once per gate by its own entry.
+struct DiagLookup {
+  uint32_t out_pos[3], out_shift[3], nout;    // op bits outside the tile: amplitude position, sub-index bit
+  uint32_t lane_bit[3], lane_shift[3], nlane; // op bits on lane bits: tile bit, sub-index bit
+  uint32_t elem_sub;                          // 3 bits per element: the sub-index part of its pass bits
+  uint32_t pad_[2];
+};
+template <int FORM>
+__global__ __launch_bounds__(256, 5) void k_diag8(A* __restrict__ st, Hp hp, uint32_t ngates, const TileDiagItem<double>* __restrict__ steps,
+                                                  const DiagLookup* __restrict__ look, const A* __restrict__ tables) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char raw[];
+  A* tile = reinterpret_cast<A*>(raw);
+  const uint32_t tid = threadIdx.x, lane = tid & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const uint64_t base = tile_base(blockIdx.x, hp);
+  A x[8];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) x[u] = ldg<true>(st + (base | row_off(u, wave, hp)) + lane);
+  const uint32_t slot_tid = tile_slot<A>(tid);
+#pragma unroll
+  for (int u = 0; u < 8; ++u) tile[slot_tid ^ tile_slot<A>((uint32_t)u << 8)] = x[u];
+  __syncthreads();
+  A e[8];
+  const uint32_t tb = tid;  // lane bits = tile bits 0..7, pass bits 8, 9, 10
+#pragma unroll
+  for (int i = 0; i < 8; ++i) e[i] = tile[slot_tid ^ tile_slot<A>((uint32_t)i << 8)];
+  if (FORM == 0) {
+    const TileDiagItem<double>* ip = steps;
+    const TileDiagItem<double>* const iend = ip + 8u * ngates;
+    for (; ip != iend;) {
+      const TileDiagItem<double> it = *ip;
+      ++ip;
+      if ((base & it.omask) != it.oval) continue;
+      A f = it.f1;
+      if (it.lane_mask != 0u) {
+        QIP_KEEP_BRANCH();
+        const bool lane_ok = (tb & it.lane_mask) == it.lane_val;
+        f.x = lane_ok ? f.x : 1.0;
+        f.y = lane_ok ? f.y : 0.0;
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        if ((it.emask_sel >> i) & 1u) {
+          QIP_KEEP_BRANCH();
+          cscale_inplace(f, e[i]);
+        }
+    }
+  } else {
+#pragma nounroll
+    for (uint32_t g = 0; g < ngates; ++g) {
+      const DiagLookup d = look[g];  // wave-uniform
+      uint32_t sub = 0;
+#pragma unroll
+      for (uint32_t j = 0; j < 3; ++j)
+        if (j < d.nout) sub |= (uint32_t)((base >> d.out_pos[j]) & 1ull) << d.out_shift[j];
+#pragma unroll
+      for (uint32_t j = 0; j < 3; ++j)
+        if (j < d.nlane) sub |= ((tb >> d.lane_bit[j]) & 1u) << d.lane_shift[j];
+      const A* tab = tables + 8u * g;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        e[i] = cmul(tab[sub | ((d.elem_sub >> (3 * i)) & 7u)], e[i]);
+        if (i & 1) __builtin_amdgcn_sched_barrier(0);  // two table reads in flight: all eight spill under the five-blocks register bound
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) tile[slot_tid ^ tile_slot<A>((uint32_t)i << 8)] = e[i];
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < 8; ++u) x[u] = tile[slot_tid ^ tile_slot<A>((uint32_t)u << 8)];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) stg<true>(st + (base | row_off(u, wave, hp)) + lane, x[u]);
+}
+
 __global__ void k_init(A* st, uint64_t n) {
   for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
     A v;
@@ -557,6 +642,60 @@ int main(int argc, char** argv) {
   const Hp mix = make_hp({12, 15, 18, 21, 24});
 #define DMA_ATTR(P, G) CK(hipFuncSetAttribute((const void*)k_dma<P, G, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536))
   DMA_ATTR(1, 0); DMA_ATTR(1, 2); DMA_ATTR(2, 8); DMA_ATTR(2, 32); DMA_ATTR(2, 64);
+  if (argc > 3 && !strcmp(argv[3], "diag8")) {
+    // sub-index bit 2 (MSB) = the outside position, bit 1 = tile bit 3 (a lane bit), bit 0 = tile bit 8 (a pass bit: element bit 0)
+    const Hp hp = make_hp({11, 12, 13, 14, 15});  // tile bit 8 = position 13
+    const uint32_t opos = (uint32_t)n - 1;
+    const uint64_t ntiles = g_n >> 11;
+    for (uint32_t D : {1u, 4u, 16u}) {
+      std::vector<TileDiagItem<double>> steps;
+      std::vector<DiagLookup> look;
+      std::vector<A> tables;
+      for (uint32_t g = 0; g < D; ++g) {
+        DiagLookup d;
+        memset(&d, 0, sizeof d);
+        d.nout = 1; d.out_pos[0] = opos; d.out_shift[0] = 2;
+        d.nlane = 1; d.lane_bit[0] = 3; d.lane_shift[0] = 1;
+        for (int i = 0; i < 8; ++i) d.elem_sub |= (uint32_t)(i & 1) << (3 * i);
+        look.push_back(d);
+        for (uint32_t sub = 0; sub < 8; ++sub) {
+          A f;
+          f.x = cos(0.1 * (sub + 1) + 0.01 * g);
+          f.y = sin(0.1 * (sub + 1) + 0.01 * g);
+          tables.push_back(f);
+          TileDiagItem<double> t;
+          memset(&t, 0, sizeof t);
+          t.f0 = t.f1 = f;
+          t.omask = 1ull << opos;
+          t.oval = (uint64_t)((sub >> 2) & 1u) << opos;
+          t.lane_mask = 1u << 3;
+          t.lane_val = ((sub >> 1) & 1u) << 3;
+          uint32_t emask = 0;
+          for (int i = 0; i < 8; ++i)
+            if ((uint32_t)(i & 1) == (sub & 1u)) emask |= 1u << i;
+          t.emask_sel = emask;
+          t.reg_pack = (1u << 8) | ((sub & 1u) << 8 << 16);
+          steps.push_back(t);
+        }
+      }
+      TileDiagItem<double>* dsteps;
+      DiagLookup* dlook;
+      A* dtab;
+      CK(hipMalloc(&dsteps, steps.size() * sizeof steps[0]));
+      CK(hipMalloc(&dlook, look.size() * sizeof look[0]));
+      CK(hipMalloc(&dtab, tables.size() * sizeof tables[0]));
+      CK(hipMemcpy(dsteps, steps.data(), steps.size() * sizeof steps[0], hipMemcpyHostToDevice));
+      CK(hipMemcpy(dlook, look.data(), look.size() * sizeof look[0], hipMemcpyHostToDevice));
+      CK(hipMemcpy(dtab, tables.data(), tables.size() * sizeof tables[0], hipMemcpyHostToDevice));
+      run("diag8 steps (expansion)", 1, (int)D, "u11-15", [&] { hipLaunchKernelGGL((k_diag8<0>), dim3((unsigned)ntiles), dim3(256), 32768, 0, g_st, hp, D, dsteps, dlook, dtab); });
+      run("diag8 table lookup", 1, (int)D, "u11-15", [&] { hipLaunchKernelGGL((k_diag8<1>), dim3((unsigned)ntiles), dim3(256), 32768, 0, g_st, hp, D, dsteps, dlook, dtab); });
+      CK(hipFree(dsteps));
+      CK(hipFree(dlook));
+      CK(hipFree(dtab));
+    }
+    CK(hipFree(g_st));
+    return 0;
+  }
   if (argc > 3 && !strcmp(argv[3], "light")) {
     const uint32_t N = (uint32_t)n;
     struct { std::vector<uint32_t> h; const char* name; } sets[] = {
