@@ -144,7 +144,10 @@ pub fn apply_op_row<E: HipElement + Default>(
 
 /// The same on device slices: `d_in` / `d_out` are device pointers to `in_len` / `out_len` elements on `device`, `stream`
 /// a `hipStream_t` (null = the null stream).  A dense op on <= 4 qubits (complex `E`: <= 3) or a `Swap`, <= 4 indices with
-/// the controls, is one asynchronous launch for every `E`, complex included; anything wider synchronises the stream.
+/// the controls, is one asynchronous launch for every `E`, complex included.  A larger payload (a wider dense table, a
+/// `SparseMatrix`) is kept on the device by the library, keyed by its content: the first call with it uploads it (and fails
+/// on a stream that is being captured), every later one is one asynchronous launch too (global option
+/// `slice_payload_cache_mb` bounds the cache; beyond it such a call uploads per call and synchronises the stream).
 ///
 /// # Safety
 /// The pointers must be valid device allocations of the stated lengths that do not alias.

@@ -107,6 +107,10 @@ int qip_hip_abi_version(void);
  *                          passes ("tile" = 1: only across gates that commute exactly) and, for "tile" = 2 from n = 24, picks
  *                          the shortest of three position-claiming plans; 0 first come, circuit order; 2 search at every size.
  *   "jit_cache_cap"        bound of the in-process cache of run-time-compiled kernels (default 512; qip_hip_jit_cache_info).
+ *   "slice_payload_cache_mb" bound in MiB of the device-resident op payloads that qip_hip_apply_op_device keeps (default 256).
+ *                          Nothing is evicted: a payload that would exceed the bound is uploaded per call instead.  0
+ *                          synchronises the devices that hold entries, FREES every entry and disables the cache — every
+ *                          hipGraph recorded from such calls must be gone by then.  Negative: QIP_ERR_INVALID.
  *   "jit_disk_cache"       1 (default) / 0: keep code objects on disk (qip_hip_jit_stats2).
  *   "jit_disk_cap_mb"      bound of that directory in MiB; oldest files go first (default -1 = $QIP_HIP_CACHE_MAX_MB or 1024;
  *                          0 = unbounded).
@@ -155,14 +159,25 @@ int qip_hip_apply_op_host(int dtype, uint32_t n, const qip_op* op,
 /* The same two functions on DEVICE slices, for any `P` of enum qip_dtype: `d_in` / `d_out` are device pointers to in_len /
  * out_len elements (not aliasing), `stream` a hipStream_t (NULL: the null stream) on `device`.  Every output row is the
  * reference's literal fold (one lane per row, columns in iterator order), so the result is bit-equal to the reference's for
- * every op kind, window and `P`.  A dense op on k <= 4 qubits (complex `P`: k <= 3, a 4-qubit table of Complex<f64> is
- * 4 KiB) and Swap, with or without controls, up to 4 indices in all, travel in the kernel arguments — the call only launches
- * on `stream` (no handle, no allocation, no copy: it can be recorded into a hipGraph) and returns without synchronising;
- * over the whole vector such an op on distinct qubits reads every input once (16-byte accesses).  Everything else is
- * uploaded per call and the call synchronises `stream` before it returns: larger dense tables and SparseMatrix rows (real /
- * integer `P`: into a buffer of the call; complex `P`: the state path's literal kernel through a temporary handle, also for
- * ops on more than 4 indices and under the global option force_generic).  A complex amplitude vector that takes many ops
- * still belongs in a state (qip_hip_state_wrap adopts device memory): that is where the in-place kernels and fusion are. */
+ * every op kind, window and `P`.
+ *   Launch only.  A dense op on k <= 4 qubits (complex `P`: k <= 3, a 4-qubit table of Complex<f64> is 4 KiB) and Swap, with
+ * or without controls, travel in the kernel arguments: the call is ONE kernel launch on `stream` and nothing else (no handle, no
+ * allocation, no copy, no synchronisation; it can be recorded into a hipGraph).  Over the whole vector such an op on distinct
+ * qubits, up to 4 indices in all, reads every input once (16-byte accesses).
+ *   Larger payloads — a wider dense table, every SparseMatrix — are kept ON THE DEVICE by the library, in a process-wide
+ * cache keyed by their CONTENT (device, `P`, op kind, number of op qubits and the payload bytes, compared in full: rewriting
+ * the same host buffer between calls gives the new op).  The FIRST call with a payload allocates and copies it (hipMalloc + a
+ * blocking copy): that call cannot be captured, and on a stream that is being captured it fails with QIP_ERR_DEVICE before it
+ * touches the device or the capture — issue the call once outside the capture.  EVERY LATER call with the same payload is
+ * host work (validation, a hash and a compare of the payload) and one launch on `stream`, as above; windows, repeated indices
+ * and ops on any number of indices included.  Complex `P` over the whole vector: a dense op on 4, 5 or 6 distinct qubits with
+ * any controls reads every input once (5 / 6 qubits: from n = k + 6).
+ *   The cache is bounded by the global option "slice_payload_cache_mb" and never evicts (a recorded graph may read an entry).
+ * A payload that would exceed the bound is uploaded for that call alone, and that call synchronises `stream` before it returns
+ * (real / integer `P`: into a buffer of the call; complex `P`: the state path's literal kernel through a temporary handle —
+ * also the route of every complex call under the global option force_generic).
+ *   A complex amplitude vector that takes many ops still belongs in a state (qip_hip_state_wrap adopts device memory): that
+ * is where the in-place kernels and fusion are. */
 int qip_hip_apply_op_device(int dtype, int device, void* stream, uint32_t n, const qip_op* op,
                             const void* d_in, uint64_t in_len, void* d_out, uint64_t out_len,
                             uint64_t in_off, uint64_t out_off, int accumulate);

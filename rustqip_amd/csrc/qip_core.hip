@@ -55,6 +55,7 @@ extern "C" int qip_hip_set_global_option(const char* key, int64_t value) try {
   if (!key) return fail(QIP_ERR_INVALID, "null option key");
   if (!strcmp(key, "force_generic")) { g_force_generic = value; return QIP_OK; }
   if (!strcmp(key, "jit_cache_cap")) return jit_set_cache_cap(value);
+  if (!strcmp(key, "slice_payload_cache_mb")) return slice_cache_set_cap_mb(value);
   if (!strcmp(key, "jit_disk_cap_mb")) return jit_set_disk_cap_mb(value);
   if (!strcmp(key, "jit_disk_cache")) { g_jit_disk = value != 0; return QIP_OK; }
   if (!strcmp(key, "jit_procs")) {
@@ -82,6 +83,7 @@ extern "C" int qip_hip_set_global_option(const char* key, int64_t value) try {
   if (!strcmp(key, "tile_wide_dense3_inline")) { g_tile_wide_dense3_inline = value != 0; return QIP_OK; }
   if (!strcmp(key, "tile_wide_pin")) { g_tile_wide_pin = value != 0; return QIP_OK; }
   if (!strcmp(key, "sparse_tile")) { g_sparse_tile = value != 0; return QIP_OK; }
+  if (!strcmp(key, "slice_read_once")) { g_slice_read_once = value != 0; return QIP_OK; }
   if (!strcmp(key, "debug_slice_sweeps")) {
     if (value != 0 && value != 2 && value != 4 && value != 8) return fail(QIP_ERR_INVALID, "debug_slice_sweeps is 0, 2, 4 or 8");
     g_debug_slice_sweeps = value;

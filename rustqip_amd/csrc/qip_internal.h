@@ -61,6 +61,8 @@ int fail(int code, const char* fmt, ...);
   catch (...) { return fail(QIP_ERR_INVALID, "internal error: unknown C++ exception"); }
 
 extern int64_t g_force_generic;
+int slice_cache_set_cap_mb(int64_t mb);  // global option "slice_payload_cache_mb" (qip_host.hip: payloads of the slice-level calls)
+extern int64_t g_slice_read_once;        // tuning option "slice_read_once" (qip_host.hip)
 extern uint32_t g_line_bits;
 extern int64_t g_tile_pad_from, g_tile_wave_rule, g_tile_remap, g_tile_sched;
 extern int64_t g_single_via_tile, g_single_via_tile_f32;

@@ -275,7 +275,8 @@ E apply_op_row(size_t n, const BasicMatrixOp<E>& op, const std::vector<E>& input
   return value;
 }
 /// device slices: d_in / d_out point at in_len / out_len elements on `device`; one asynchronous launch on `stream` for a dense
-/// op on <= 4 qubits (complex E: <= 3) or a Swap, <= 4 indices with the controls (include/qip_hip.h: qip_hip_apply_op_device)
+/// op on <= 4 qubits (complex E: <= 3) or a Swap — and for every larger payload (wider dense tables, SparseMatrix) from the second
+/// call on: the first uploads it into the library's payload cache and cannot be captured (include/qip_hip.h: qip_hip_apply_op_device)
 template <typename E>
 void apply_op_device(size_t n, const BasicMatrixOp<E>& op, const E* d_in, size_t in_len, E* d_out, size_t out_len,
                      size_t input_offset, size_t output_offset, bool accumulate = true, int device = 0, void* stream = nullptr) {

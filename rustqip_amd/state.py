@@ -126,10 +126,13 @@ def apply_op_device(n: int, op: MatrixOp, input, output, input_offset: int = 0, 
                     accumulate: bool = True, stream: int = 0) -> None:
     """apply_op (accumulate) / apply_op_overwrite on DEVICE slices for any `P` (qip_hip_apply_op_device): `input` / `output`
     are DeviceSlice objects or contiguous 1-D torch tensors on one GPU, `stream` a raw hipStream_t (0 = null stream).  Nothing
-    is copied to the host; with a dense op on k <= 4 qubits (complex `P`: k <= 3) or a Swap, at most 4 indices with the controls,
-    the call only launches on `stream` for every `P` — it can be recorded into a hipGraph — and over the whole vector it reads
-    each input once; SparseMatrix and wider ops synchronise the stream.  `op` may be a MatrixOp or the
-    descriptor `op.to_c(dtype)` built once (the reference's benches build their op once, outside the timed loop)."""
+    is copied to the host; with a dense op on k <= 4 qubits (complex `P`: k <= 3) or a Swap the call only launches on `stream`
+    for every `P` — it can be recorded into a hipGraph — and over the whole vector (at most 4 indices with the controls) it
+    reads each input once.  The payload of a wider dense op or a SparseMatrix is kept on the device by the library, keyed by its
+    content: the first call with it uploads it (QipHipError on a stream that is being captured), every later one only launches
+    (complex `P`: a dense op on 4 - 6 qubits reads each input once); `set_global_option("slice_payload_cache_mb", mb)` bounds
+    that cache (default 256; 0 frees it), beyond it such a call uploads per call and synchronises the stream.  `op` may be a
+    MatrixOp or the descriptor `op.to_c(dtype)` built once (the reference's benches build their op once, outside the timed loop)."""
     i, o = _as_slice(input), _as_slice(output)
     if i.dtype != o.dtype or i.device != o.device:
         raise CircuitError(f"input and output differ in element dtype or device ({i.dtype} on {i.device}, {o.dtype} on {o.device})")
