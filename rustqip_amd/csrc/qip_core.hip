@@ -47,7 +47,7 @@ int64_t g_tile_pad_from = 11, g_tile_wave_rule = 1, g_tile_remap = 0, g_tile_sch
 int64_t g_tile_row_split = 11, g_tile_row_split_f32 = 5;
 int64_t g_single_via_tile = 3, g_single_via_tile_f32 = 3;
 int64_t g_force_k4_direct = 0;
-int64_t g_collective_timeout_s = 120;  // global option "collective_timeout_s" (qip_dist.hip: how long a rank waits for an exchange)  // row bits of k_permute_bits for 16-byte elements: 0 = by the permutation, 5 / 6 = forced (tuning aid)
+int64_t g_collective_timeout_s = 120;  // global option "collective_timeout_s" (qip_dist.hip: how long a rank waits for an exchange)
 // Options (include/qip_hip.h lists the product's).  The measured alternatives of earlier rounds — each one a code path that lost
 // its A/B run (profiles/r0*_*.md) — are fixed at their defaults in the product build; a build with -DQIP_HIP_TUNING
 // (QIP_HIP_TUNING=1 python -m rustqip_amd.build) makes them switchable again for the tools/ bench scripts.

@@ -4,6 +4,7 @@
 //   qip_tile_sched.hip the host-only tile scheduler (segments, passes, relabelling, plan export)
 //   qip_circuit.hip   apply_ops: fusion, tile sweeps (interpreter + the source of run-time-compiled segments), hipGraph programs
 //   qip_jit.hip       the run-time compiler behind qip_jit.h: hiprtc, disk cache, helper processes, resident kernels, plan memo
+//   qip_slice.hip     apply_op on device slices of any element type (qip_hip_apply_op_device): payload cache, kernels, routing
 //   qip_host.hip      host-pointer twins of the reference functions
 //   qip_measure.hip   measurement
 //   qip_dist.hip      the sharded state (planner, pack sweep, exchange)
@@ -61,18 +62,18 @@ int fail(int code, const char* fmt, ...);
   catch (...) { return fail(QIP_ERR_INVALID, "internal error: unknown C++ exception"); }
 
 extern int64_t g_force_generic;
-int slice_cache_set_cap_mb(int64_t mb);  // global option "slice_payload_cache_mb" (qip_host.hip: payloads of the slice-level calls)
-extern int64_t g_slice_read_once;        // tuning option "slice_read_once" (qip_host.hip)
+int slice_cache_set_cap_mb(int64_t mb);  // global option "slice_payload_cache_mb" (qip_slice.hip: payloads of the slice-level calls)
+extern int64_t g_slice_read_once;        // tuning option "slice_read_once" (qip_slice.hip)
 extern uint32_t g_line_bits;
-extern int64_t g_tile_pad_from, g_tile_wave_rule, g_tile_remap, g_tile_sched;
-extern int64_t g_single_via_tile, g_single_via_tile_f32;
+extern int64_t g_tile_pad_from, g_tile_wave_rule, g_tile_remap, g_tile_sched;  // tuning aids of the tile sweeps (qip_hip_set_global_option)
+extern int64_t g_single_via_tile, g_single_via_tile_f32;  // 0 = never, 1 = single dense k = 2, 3 / Swap ops with a bit inside a row go as a one-item tile sweep, 2 = every dense k = 2, 3
 extern int64_t g_dist_fold_pack, g_dist_plan_cost;  // qip_dist.hip
 extern int64_t g_collective_timeout_s;             // qip_core.hip: seconds a rank waits for an exchange before it fails (0 = for ever)
 extern int64_t g_sparse_tile;  // qip_launch.hip
 extern int64_t g_soft_measure_one_pass;  // qip_measure.hip
 extern int64_t g_tile_wide_pin, g_tile_wide_dense3_inline;  // qip_circuit.hip
 extern int64_t g_debug_slice_sweeps;  // qip_circuit.hip
-extern int64_t g_force_k4_direct;  // tuning aid: dense k = 4 on the matrix cores reads its operands straight from HBM (k_gate_kq_mfma)  // 0 = never, 1 = single dense k = 2, 3 / Swap ops with a bit inside a row go as a one-item tile sweep, 2 = every dense k = 2, 3  // tuning aids of the tile sweeps (qip_hip_set_global_option)
+extern int64_t g_force_k4_direct;  // tuning aid: dense k = 4 on the matrix cores reads its operands straight from HBM (k_gate_kq_mfma)
 
 struct FlatOp {
   const qip_op* outer = nullptr;
@@ -166,10 +167,10 @@ struct qip_hip_state {
   int64_t profile = 0;
   int64_t lowbit_shuffle = 1;
   int64_t mfma = 1;
-  int64_t fuse = 0;
+  int64_t fuse = 0;  // 0 = gate by gate; K >= 2 = fuse into dense gates on <= K qubits
   int64_t tile_passes = 1;  // tile sweeps: group gates into register passes (k_tile_passes) vs one LDS pass per gate
   int64_t tile = 0;  // 0 off, 1 = LDS-resident multi-gate sweeps in circuit order, 2 = with commuting reorder
-  int64_t packed_f32 = 1;
+  int64_t packed_f32 = 1;  // f32: sweep two amplitudes per 16-B element when bit 0 is not involved
   int64_t tile_relabel = 0;  // tile sweeps: the scheduler relabels the qubits (schedule_tiles_relabel); 3 = the layout persists
   // Persistent relabelling (tile_relabel = 3): layout[p] = physical position of logical index bit p, in force BETWEEN
   // apply_ops calls (empty = the caller's order).  Everything that reads, writes or addresses amplitudes other than a
@@ -193,7 +194,7 @@ struct qip_hip_state {
   // program capture (hipGraph): non-null while a program records its launches.  Op payloads then go to the PROGRAM's own
   // device pool instead of the arena (ProgPool below): the graph holds kernel nodes only and replays nothing from the host.
   struct ProgPool* capture_pool = nullptr;
-  std::vector<struct qip_hip_program*> programs;  // graphs recorded against this state's buffers  // f32: sweep two amplitudes per 16-B element when bit 0 is not involved  // 0 = gate by gate; K >= 2 = fuse into dense gates on <= K qubits
+  std::vector<struct qip_hip_program*> programs;  // graphs recorded against this state's buffers
   int64_t unroll = 0;  // 0 = default per kernel
   // profiling
   std::vector<ProfRec> pending;
@@ -310,6 +311,8 @@ template <typename T> int apply_op_t(qip_hip_state* s, const qip_op* op, const B
 // (its bits would change).
 enum class SingleRoute { kOwnKernel, kTileSweep, kMatrixCores };
 SingleRoute single_route(const qip_hip_state* s, const qip_op* op);
+// the literal gather kernels' descriptor of one call (k_gather_generic; k_gather_real / k_gather_cplx of qip_slice.hip)
+GatherDesc make_gather_desc(uint32_t n, const FlatOp& f, uint64_t in_len, uint64_t out_len, uint64_t in_off, uint64_t out_off, int accumulate);
 template <typename T>
 int launch_gather(qip_hip_state* s, const FlatOp& f, const amp_t<T>* in, uint64_t in_len, amp_t<T>* out, uint64_t out_len,
                   uint64_t in_off, uint64_t out_off, int accumulate);
@@ -319,5 +322,13 @@ template <typename T> static amp_t<T> mk(double re, double im) {
   a.x = (T)re;
   a.y = (T)im;
   return a;
+}
+static inline size_t elem_bytes(int dtype) {  // of the slice-level calls' element types; 0 = not one
+  switch (dtype) {
+    case QIP_C64: return 16;
+    case QIP_C32: case QIP_F64: case QIP_I64: return 8;
+    case QIP_F32: case QIP_I32: return 4;
+    default: return 0;
+  }
 }
 static inline bool use_nt(const qip_hip_state* s) { return s->namps * s->amp_bytes >= (1ull << 30); }

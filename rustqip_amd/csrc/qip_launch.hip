@@ -1064,14 +1064,10 @@ static int launch_kq(qip_hip_state* s, const Plan& p, amp_t<T>* st, int* actual_
   return QIP_OK;
 }
 
-// Ship the inner op's payload to the arena and run the literal gather kernel in -> out.
-template <typename T>
-int launch_gather(qip_hip_state* s, const FlatOp& f, const amp_t<T>* in, uint64_t in_len,
-                         amp_t<T>* out, uint64_t out_len, uint64_t in_off, uint64_t out_off,
-                         int accumulate) {
+GatherDesc make_gather_desc(uint32_t n, const FlatOp& f, uint64_t in_len, uint64_t out_len, uint64_t in_off, uint64_t out_off, int accumulate) {
   GatherDesc d;
   memset(&d, 0, sizeof d);
-  d.n = s->n;
+  d.n = n;
   d.k_all = f.k_all;
   d.n_control = f.n_control;
   d.n_op = f.n_op;
@@ -1081,7 +1077,16 @@ int launch_gather(qip_hip_state* s, const FlatOp& f, const amp_t<T>* in, uint64_
   d.out_len = out_len;
   d.in_off = in_off;
   d.out_off = out_off;
-  for (uint32_t j = 0; j < f.k_all; ++j) d.pos[j] = (uint32_t)(s->n - 1 - f.outer->indices[j]);
+  for (uint32_t j = 0; j < f.k_all; ++j) d.pos[j] = (uint32_t)(n - 1 - f.outer->indices[j]);
+  return d;
+}
+
+// Ship the inner op's payload to the arena and run the literal gather kernel in -> out.
+template <typename T>
+int launch_gather(qip_hip_state* s, const FlatOp& f, const amp_t<T>* in, uint64_t in_len,
+                         amp_t<T>* out, uint64_t out_len, uint64_t in_off, uint64_t out_off,
+                         int accumulate) {
+  const GatherDesc d = make_gather_desc(s->n, f, in_len, out_len, in_off, out_off, accumulate);
   const amp_t<T>* dense = nullptr;
   const uint64_t* rowptr = nullptr;
   const uint64_t* cols = nullptr;

@@ -21,7 +21,12 @@ class Buf:
         self.dtype, self.length, self.nbytes = arr.dtype, arr.size, arr.nbytes
         m = max(1, int(np.ceil(np.log2(max(arr.nbytes, 32) / 16))))
         self.st = q.HipState(m)
-        raw = np.zeros((1 << m) * 16, dtype=np.uint8)
+        self.put(arr)
+
+    def put(self, arr):
+        """new contents of the same type and size"""
+        assert arr.dtype == self.dtype and arr.nbytes == self.nbytes
+        raw = np.zeros((1 << self.st.n) * 16, dtype=np.uint8)
         raw[:arr.nbytes] = np.ascontiguousarray(arr).view(np.uint8).ravel()
         self.st.upload(raw.view(np.complex128))
         self.st.sync()
@@ -156,6 +161,81 @@ def test_whole_vector_group_kernel_every_shape(O, dtype):
                     q.set_global_option("force_generic", 0)
             for got in outs:
                 assert np.array_equal(got, want, equal_nan=True) and np.array_equal(np.signbit(got), np.signbit(want)) if not integer else np.array_equal(got, want), (op, dtype, acc)
+
+
+def small_vector_shapes(n, rng, vals):
+    """every (indices, controls, kind) shape on K = 1..min(n, 4) distinct indices of an n-qubit vector with the lowest index bit at
+    position 0, 1 and 2 (where n - K leaves room), and the pair on positions 0 and 1 in both orders"""
+    shapes = []
+    for low_pos in range(min(n, 3)):
+        low = n - 1 - low_pos  # (qubit index; the indices below it are the positions above)
+        for k_all in range(1, min(low + 1, 4) + 1):
+            idx = [int(v) for v in rng.permutation(low)[:k_all - 1]] + [low]
+            rng.shuffle(idx)
+            for nc in range(k_all):
+                k_op = k_all - nc
+                inner = MatrixOp.new_matrix(idx[nc:], vals(4 ** k_op))
+                shapes.append(inner if nc == 0 else MatrixOp.new_control(idx[:nc], idx[nc:], inner))
+                if k_op % 2 == 0:
+                    sw = MatrixOp.new_swap(idx[nc:nc + k_op // 2], idx[nc + k_op // 2:])
+                    shapes.append(sw if nc == 0 else MatrixOp.new_control(idx[:nc], idx[nc:], sw))
+    for a_, b_ in ((n - 1, n - 2), (n - 2, n - 1)):
+        shapes += [MatrixOp.new_matrix([a_, b_], vals(16)), MatrixOp.new_swap([a_], [b_]),
+                   MatrixOp.new_control([a_], [b_], MatrixOp.new_matrix([b_], vals(4)))]
+        if n >= 3:
+            shapes += [MatrixOp.new_matrix([a_, 0, b_], vals(64)), MatrixOp.new_control([0], [a_, b_], MatrixOp.new_swap([a_], [b_]))]
+    return shapes
+
+
+@pytest.mark.parametrize("dtype", REAL_TYPES + (np.complex128, np.complex64))
+def test_small_vectors_reach_the_edges_of_the_group_geometry(O, dtype):
+    """both windows = the whole vector of n = 2..6 qubits (at most 64 elements), every element type: K = n (no group: the literal
+    kernel), n = K + 1 and n = K + 2 (the admission bounds of the vector, pair and low forms), accumulate and overwrite, with a
+    -0.0 and an inf in the input — bit-equal (values, NaNs, signs of zero) to the oracle and to the literal kernel (force_generic)"""
+    from test_gpu_a_complex_slices import same as same_complex
+
+    rng = np.random.default_rng(41)
+    integer = np.issubdtype(dtype, np.integer)
+    cplx = np.issubdtype(dtype, np.complexfloating)
+
+    def vals(c):
+        if integer:
+            return rng.integers(-3, 4, size=c).astype(float)
+        return rng.standard_normal(c) + 1j * rng.standard_normal(c) if cplx else rng.standard_normal(c)
+
+    def same(got, want):
+        if integer:
+            return np.array_equal(got, want)
+        if cplx:
+            return same_complex(got, want)
+        return np.array_equal(got, want, equal_nan=True) and np.array_equal(np.signbit(got), np.signbit(want))
+
+    for n in range(2, 7):
+        N = 1 << n
+        d_in, d_out = Buf(np.zeros(N, dtype=dtype)), Buf(np.zeros(N, dtype=dtype))  # (one pair per size: a shape costs uploads only)
+        try:
+            for op in small_vector_shapes(n, rng, vals):
+                x, y0 = vector(rng, N, dtype), vector(rng, N, dtype)
+                if cplx:
+                    x[1], x[N - 1] = complex(-0.0, 1.5), complex(np.inf, -0.25)
+                elif not integer:
+                    x[1], x[N - 1] = -0.0, np.inf
+                d_in.put(x)
+                for acc in (True, False):
+                    want = y0.copy()
+                    O.apply_op(n, op, x, want, accumulate=acc)
+                    outs = []
+                    for generic in (0, 1):
+                        q.set_global_option("force_generic", generic)
+                        try:
+                            d_out.put(y0)
+                            q.apply_op_device(n, op, d_in.slice(), d_out.slice(), accumulate=acc)
+                            outs.append(d_out.get())
+                        finally:
+                            q.set_global_option("force_generic", 0)
+                    assert same(outs[0], want) and same(outs[1], want) and same(outs[0], outs[1]), (n, op, dtype, acc)
+        finally:
+            d_in.close(), d_out.close()
 
 
 @pytest.mark.parametrize("dtype", (np.int64, np.int32))

@@ -12,8 +12,8 @@ Ops whose payload lives in the library's device-resident cache (a dense op on >=
   python tools/bench_complex_slices.py --payloads [n] [rounds] [--parent-lib libqip_hip.so] [--tuning-lib libqip_hip.so]
 
 One process per library and round, the libraries alternating; per shape the median and the range over the rounds of the wall
-time per call (a call and a stream synchronisation) and of the HIP-event time.  --parent-lib: the parent commit's build, whose
-calls upload and synchronise.  --tuning-lib: a -DQIP_HIP_TUNING build of this tree, run with option slice_read_once = 0 — every
+time per call (a call and a stream synchronisation) and of the HIP-event time.  --parent-lib: the parent commit's build (its
+calls only launch, as this tree's do: they are recorded into the hipGraph too).  --tuning-lib: a -DQIP_HIP_TUNING build of this tree, run with option slice_read_once = 0 — every
 cached payload through the literal pointer launch (k_gather_cplx), the yardstick of the read-once kernels.  The launch-bound
 shapes (a dense 8-qubit op at n = 8, a sparse 16-qubit op at n = 16) are timed call by call, as host time per call without a
 synchronisation beside that of an op whose table travels in the kernel arguments (the difference is the hash and the compare of
@@ -216,8 +216,6 @@ def payload_main(args):
                 env["QIP_HIP_LIB"] = libs[lib]
             if lib == "literal":
                 env["QIP_BENCH_READ_ONCE"] = "0"
-            if lib == "parent":
-                env["QIP_BENCH_CAPTURE"] = "0"  # (its calls synchronise: they cannot be recorded)
             p = subprocess.run([sys.executable, __file__, "--payload-worker", str(n)], env=env, capture_output=True, text=True, timeout=280)
             line = [ln for ln in p.stdout.splitlines() if ln.startswith("PAYLOADS ")]
             if p.returncode != 0 or not line:
@@ -239,14 +237,14 @@ def payload_main(args):
         ev = statistics.median([run[key]["event_us"] for run in runs["new"]])
         print(f"| {m} | {dt} | {name} | {acc} | " + " | ".join(cells) + (f" | {by / ev / 1e3:.0f} |" if int(m) > 20 else " | — |"))
     print("\nlaunch-bound shapes: host us per call without a synchronisation; us per call inside a 64-call hipGraph\n")
-    print("| n | op | " + " | ".join(f"{k}: host" for k in order) + " | " + " | ".join(f"{k}: in a graph" for k in order if k != "parent") + " |")
-    print("|---|---|" + "---|" * (2 * len(order) - (1 if "parent" in order else 0)))
+    print("| n | op | " + " | ".join(f"{k}: host" for k in order) + " | " + " | ".join(f"{k}: in a graph" for k in order) + " |")
+    print("|---|---|" + "---|" * (2 * len(order)))
     for key in runs["new"][0]:
         if "host_us" not in runs["new"][0][key]:
             continue
         m, dt, name, acc = key.split("|")
         cells = [stat([run[key]["host_us"] for run in runs[k]]) for k in order]
-        cells += [stat([run[key]["graph_us"] for run in runs[k]]) for k in order if k != "parent"]
+        cells += [stat([run[key]["graph_us"] for run in runs[k]]) for k in order]
         print(f"| {m} | {name} | " + " | ".join(cells) + " |")
     return 0
 

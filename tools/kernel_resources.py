@@ -22,7 +22,7 @@ def main():
     res = "/tmp/qip_kernel_resources.txt"
     if not (len(sys.argv) > 1 and sys.argv[1] == "--cached" and os.path.exists(res)):
         with open(res, "w") as f:
-            for unit in ("qip_launch", "qip_circuit", "qip_host", "qip_measure", "qip_dist"):  # the translation units that launch kernels
+            for unit in ("qip_launch", "qip_circuit", "qip_slice", "qip_host", "qip_measure", "qip_dist"):  # the translation units that launch kernels
                 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC",
                        "-c", "-o", "/tmp/qip_res.o", os.path.join(ROOT, "rustqip_amd", "csrc", unit + ".hip"),
                        "-Rpass-analysis=kernel-resource-usage"]
