@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 # one translation unit per concern (csrc/qip_internal.h lists them); compiled in parallel, linked into ONE library whose
 # only exports are the C ABI (csrc/exports.map)
-UNITS = ["qip_core", "qip_launch", "qip_tile_sched", "qip_circuit", "qip_jit", "qip_slice", "qip_host", "qip_measure", "qip_dist"]
+UNITS = ["qip_core", "qip_launch", "qip_tile_sched", "qip_circuit", "qip_tile_interp", "qip_jit", "qip_slice", "qip_host", "qip_measure", "qip_dist"]
 HEADERS = [os.path.join(CSRC, h) for h in ("qip_kernels.h", "qip_internal.h", "qip_jit.h", "qip_tile.h")] + [
     os.path.join(HERE, "..", "include", "qip_hip.h"), os.path.join(HERE, "..", "include", "qip_hip_debug.h")]
 OBJDIR = os.path.join(HERE, "build")
@@ -28,6 +28,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fn
 # (csrc/qip_core.hip, "tuning options"): what tools/bench_ops.py, bench_tile.py, bench_permute.py switch for A/B runs
 if os.environ.get("QIP_HIP_TUNING"):
     FLAGS.append("-DQIP_HIP_TUNING")
+# Options of single units.  qip_tile_interp holds one kernel family, k_tile_passes, whose branches are all wave-uniform: left
+# unstructured (hipcc structurizes uniform regions too by default) its gate loop keeps the lane's amplitudes in one register set
+# instead of copying them between two at every gate (csrc/qip_tile_interp.hip, profiles/gate_loop_copies.md).  The option is
+# given to no unit with a divergent branch, and run-time-compiled segments have their own options (csrc/qip_jit.hip).
+UNIT_FLAGS = {"qip_tile_interp": ["-mllvm", "-structurizecfg-skip-uniform-regions"]}
 LINK = ["--offload-arch=gfx950", "-fPIC", "-shared", "-Wl,--version-script=" + os.path.join(CSRC, "exports.map")]
 LIBS = ["-ldl"]  # librccl and libhiprtc are dlopen-ed on first use (qip_dist.hip, qip_jit.hip): no link-time dependency
 
@@ -66,7 +71,7 @@ def build(force: bool = False) -> str:
         src, obj = os.path.join(CSRC, u + ".hip"), os.path.join(OBJDIR, u + ".o")
         deps = [src] + HEADERS + ([EMBED] if u == "qip_jit" else [])
         if force or _stale(obj, deps):
-            jobs.append([HIPCC, *FLAGS, "-c", src, "-o", obj])
+            jobs.append([HIPCC, *FLAGS, *UNIT_FLAGS.get(u, []), "-c", src, "-o", obj])
     if jobs:
         from concurrent.futures import ThreadPoolExecutor
 

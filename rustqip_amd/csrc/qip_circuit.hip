@@ -969,19 +969,8 @@ static int launch_tile_segment(qip_hip_state* s, const BatchRun& run, const std:
     return run_parts(s, run, f, &rec, [&](uint32_t k) -> int {
       Ins ins_k = ins;
       ins_k.ormask |= f.slice_or(k);
-      if (f.folding) {
-#define TPF(NTV) hipLaunchKernelGGL((k_tile_passes<T, NTV, true>), grid2d(ntiles_part, 1), dim3(kTileBlock), lds, s->stream, \
-                                    (amp_t<T>*)s->cur, ins_k, pd, dg, dmats, (amp_t<T>*)s->alt, *fold, ditems)
-        if (use_nt(s)) TPF(true);
-        else TPF(false);
-#undef TPF
-      } else {
-#define TP(NTV) hipLaunchKernelGGL((k_tile_passes<T, NTV>), grid2d(ntiles_part, 1), dim3(kTileBlock), lds, s->stream, \
-                                   (amp_t<T>*)s->cur, ins_k, pd, dg, dmats, (amp_t<T>*)nullptr, TileStorePerm(), ditems)
-        if (use_nt(s)) TP(true);
-        else TP(false);
-#undef TP
-      }
+      launch_tile_passes<T>(s->stream, grid2d(ntiles_part, 1), lds, use_nt(s), (amp_t<T>*)s->cur, ins_k, pd, dg, dmats, (amp_t<T>*)s->alt,
+                            f.folding ? fold : nullptr, ditems);
       HIPCHK(hipGetLastError());
       return QIP_OK;
     });

@@ -3,6 +3,7 @@
 //   qip_launch.hip    one launcher per kernel class, apply_op
 //   qip_tile_sched.hip the host-only tile scheduler (segments, passes, relabelling, plan export)
 //   qip_circuit.hip   apply_ops: fusion, tile sweeps (interpreter + the source of run-time-compiled segments), hipGraph programs
+//   qip_tile_interp.hip the interpreter's sweep kernel k_tile_passes and its launch (a unit of its own: it has a compile option of its own)
 //   qip_jit.hip       the run-time compiler behind qip_jit.h: hiprtc, disk cache, helper processes, resident kernels, plan memo
 //   qip_slice.hip     apply_op on device slices of any element type (qip_hip_apply_op_device): payload cache, kernels, routing
 //   qip_host.hip      host-pointer twins of the reference functions

@@ -96,7 +96,34 @@ __device__ __forceinline__ void cscale_inplace(amp_t<double> f, amp_t<double>& e
       : "+v"(e.x), "+v"(e.y), "=&v"(t0), "=&v"(t1)
       : "v"(f.x), "v"(f.y));
 }
-__device__ __forceinline__ void cscale_inplace(amp_t<float> f, amp_t<float>& e) { e = cmul(f, e); }
+__device__ __forceinline__ void cscale_inplace(amp_t<float> f, amp_t<float>& e) {
+  float t0, t1;
+  asm("v_mul_f32 %2, %4, %0\n\t"
+      "v_mul_f32 %3, %5, %1\n\t"
+      "v_mul_f32 %1, %4, %1\n\t"
+      "v_mul_f32 %0, %5, %0\n\t"
+      "v_add_f32 %1, %1, %0\n\t"
+      "v_sub_f32 %0, %2, %3"
+      : "+v"(e.x), "+v"(e.y), "=&v"(t0), "=&v"(t1)
+      : "v"(f.x), "v"(f.y));
+}
+// a <-> b IN PLACE, for the same loop: written out, an exchange of two loop-carried values makes the compiler give every
+// amplitude of the lane a second register and copy all of them back at the loop latch; here each value keeps its register.
+__device__ __forceinline__ void cswap_inplace(amp_t<double>& a, amp_t<double>& b) {
+  double t;
+  asm("v_mov_b64 %2, %0\n\t"
+      "v_mov_b64 %0, %1\n\t"
+      "v_mov_b64 %1, %2"
+      : "+v"(a.x), "+v"(b.x), "=&v"(t));
+  asm("v_mov_b64 %2, %0\n\t"
+      "v_mov_b64 %0, %1\n\t"
+      "v_mov_b64 %1, %2"
+      : "+v"(a.y), "+v"(b.y), "=&v"(t));
+}
+__device__ __forceinline__ void cswap_inplace(amp_t<float>& a, amp_t<float>& b) {
+  asm("v_swap_b32 %0, %1" : "+v"(a.x), "+v"(b.x));
+  asm("v_swap_b32 %0, %1" : "+v"(a.y), "+v"(b.y));
+}
 template <typename A> __device__ __forceinline__ A cadd(A a, A b) {
   A r;
   r.x = a.x + b.x;
@@ -1728,11 +1755,31 @@ struct TilePassDesc {
 //     into +0), the same equality the X and real-entry forms rely on;
 //   * explicit FMAs for tile = 2 (which is held to 1e-12 anyway) would halve the arithmetic, but every FMA
 //     variant of this kernel spilled under the occupancy bound (430 VGPRs at 96, 48 at 128): 30 ms per sweep;
-//   * what remains above the arithmetic is hipcc ping-ponging the lane's eight amplitudes between two register
-//     sets across the gate loop (about 16 v_mov_b64 per gate).  Tried and measured worse: the updates as in-place
-//     gfx950 inline assembly with "+v" operands (operands copied in and out: 2186 vs 1602 vector instructions
-//     per wave for 20 Hadamards), scalar re[8]/im[8] registers with products-before-sums ordering (1825, and the
-//     X exchange if-converted into selects: 2959 vs 1256);
+//   * the lane's eight amplitudes live in ONE register set across the gate loop: a gate executes its arithmetic and no copy of an
+//     amplitude it left alone.  (Until this was settled hipcc kept them twice, a set the loop header and every case read and a set
+//     the cases wrote: 16 v_mov_b64 at the loop latch for every gate, 48 more on entering a diagonal run, a third of the vector
+//     issue slots of an H / Rz circuit.)  Two things make it so, and both are needed:
+//       - the kernel is compiled in a unit of its own (qip_tile_interp.hip) with uniform regions left unstructured.  Every branch
+//         here is wave-uniform, but hipcc's default pipeline structurizes the gate loop all the same, and the flow blocks it
+//         inserts merge the amplitudes through PHIs with undefined inputs that the register coalescer cannot join.  With the
+//         switch reduced to the four paths of an H / Rz circuit, every one of them in place, the copies were still all there;
+//       - no case body defines an amplitude's new value while the old one is still needed (the template parameter LOOP / INPLACE
+//         of the pass_* functions, set by this kernel only: generated segments are straight-line code and keep the plain forms).
+//         One body that does gives that amplitude a second register, and the copy back lands on the latch, for every gate:
+//         cmul(f, e) assigned to e (now cscale_inplace), a row of a dense gate assigned before the other row has read the pair
+//         (14 latch copies; now products first, pass_dense_body), an exchange of two elements written as three assignments (2
+//         for X, 4 for swap; now cswap_inplace).
+//     Tried before that and measured worse: the updates of dense gates as in-place inline assembly with "+v" operands (operands
+//     copied in and out: 2186 vs 1602 vector instructions per wave for 20 Hadamards), scalar re[8]/im[8] registers with
+//     products-before-sums ordering (1825, and the X exchange if-converted into selects: 2959 vs 1256).  Without effect under
+//     the structurizer: deleting the dense 2- / 3-qubit, swap and lane-control cases (same 16 + 48 copies), one diagonal item per
+//     loop trip instead of an inner loop (48 -> 32 at the run entry, + 4 per skipped element).  Complex<f32>: the dense 2-qubit
+//     case alone still ends in a copy of the eight amplitudes (8 v_mov_b64 in front of the latch, executed by that case only);
+//     raising the coalescer's large-interval limit halves that kernel's remaining copies but triples the unit's compile time:
+//     not taken.  Not done: ordering the
+//     dispatch so that the commonest ops (6 - 8, 27, 0, 1) resolve first; the switch is a binary compare tree of four to five
+//     scalar compare-and-branch pairs per gate, against 32 - 48 vector instructions.  tools/kernel_resources.py --isa prints the
+//     counts and the latch;
 //   * a dense gate whose second row is its first up to one sign per column (H, H.X after tile_absorb_x, Ry(pi/2)) multiplies
 //     once for both rows: (-m)*x is -(m*x) in every bit and the negation rides on the add as a source modifier, so a Hadamard is
 //     16 mul + 16 add per lane instead of 32 + 16.  The four sign patterns are four straight-line variants behind scalar branches
@@ -1749,30 +1796,35 @@ template <typename A> __device__ __forceinline__ A tile_sel(bool take, A yes, A 
   return r;
 }
 
+// one product of a 2x2 gate's entry and an amplitude; REAL: the entry is (re, 0)
+template <typename T, bool REAL> __device__ __forceinline__ amp_t<T> tile_prod(amp_t<T> m, amp_t<T> x) {
+  if constexpr (REAL) {
+    amp_t<T> r;
+    r.x = m.x * x.x;
+    r.y = m.x * x.y;
+    return r;
+  } else {
+    return cmul(m, x);
+  }
+}
+
 // one row of a 2x2 gate applied to the pair (a0, a1), zero entries skipped; REAL: every entry is (re, 0)
 template <typename T, bool REAL>
 __device__ __forceinline__ amp_t<T> tile_row(amp_t<T> ma, amp_t<T> mb, bool has_a, bool has_b, amp_t<T> a0, amp_t<T> a1) {
   using A = amp_t<T>;
-  auto prod = [](A m, A x) {
-    if constexpr (REAL) {
-      A r;
-      r.x = m.x * x.x;
-      r.y = m.x * x.y;
-      return r;
-    } else {
-      return cmul(m, x);
-    }
-  };
-  if (has_a && has_b) return cadd(prod(ma, a0), prod(mb, a1));
-  if (has_a) return prod(ma, a0);
-  if (has_b) return prod(mb, a1);
+  if (has_a && has_b) return cadd(tile_prod<T, REAL>(ma, a0), tile_prod<T, REAL>(mb, a1));
+  if (has_a) return tile_prod<T, REAL>(ma, a0);
+  if (has_b) return tile_prod<T, REAL>(mb, a1);
   return czero<A>();
 }
 
 // dense 1-qubit gate on pass bit J: four register butterflies.  c[i] = the pass-bit part of element i's tile
 // index (wave-uniform), cm = the gate's controls that sit on pass bits.  The common shapes (no control on a pass
 // bit, all four entries non-zero) run as straight-line code; every test below is wave-uniform.
-template <typename T, int J, bool REAL, bool CHECKED, int NE>
+// LOOP (the interpreter's gate loop, whose header, cases and latch must agree on ONE register per amplitude): every product of
+// the pair is formed before the first output is assigned, so no new value is defined while the one it replaces is still
+// needed and the outputs can take the inputs' registers.  The products and sums per output, and their order, are the same.
+template <typename T, int J, bool REAL, bool CHECKED, int NE, bool LOOP = false>
 __device__ __forceinline__ void pass_dense_body(const TileGate<T>& g, amp_t<T> (&e)[NE], const uint32_t (&c)[NE], uint32_t cm) {
   using A = amp_t<T>;
   const bool h0 = CHECKED ? (g.nz & 1u) != 0 : true, h1 = CHECKED ? (g.nz & 2u) != 0 : true;
@@ -1786,8 +1838,27 @@ __device__ __forceinline__ void pass_dense_body(const TileGate<T>& g, amp_t<T> (
       QIP_KEEP_BRANCH();
     }
     const A a0 = e[i], a1 = e[k];
-    e[i] = tile_row<T, REAL>(g.m[0], g.m[1], h0, h1, a0, a1);
-    e[k] = tile_row<T, REAL>(g.m[2], g.m[3], h2, h3, a0, a1);
+    if constexpr (LOOP && !CHECKED) {
+      const A q0 = tile_prod<T, REAL>(g.m[0], a0), q1 = tile_prod<T, REAL>(g.m[1], a1);
+      const A q2 = tile_prod<T, REAL>(g.m[2], a0), q3 = tile_prod<T, REAL>(g.m[3], a1);
+      __builtin_amdgcn_sched_barrier(0);
+      e[i] = cadd(q0, q1);
+      e[k] = cadd(q2, q3);
+    } else if constexpr (LOOP) {  // tile_row's four shapes per row, the products first
+      A q0 = czero<A>(), q1 = czero<A>(), q2 = czero<A>(), q3 = czero<A>();
+      if (h0) { QIP_KEEP_BRANCH(); q0 = tile_prod<T, REAL>(g.m[0], a0); }
+      if (h1) { QIP_KEEP_BRANCH(); q1 = tile_prod<T, REAL>(g.m[1], a1); }
+      if (h2) { QIP_KEEP_BRANCH(); q2 = tile_prod<T, REAL>(g.m[2], a0); }
+      if (h3) { QIP_KEEP_BRANCH(); q3 = tile_prod<T, REAL>(g.m[3], a1); }
+      __builtin_amdgcn_sched_barrier(0);
+      if (h0 && h1) { QIP_KEEP_BRANCH(); e[i] = cadd(q0, q1); }
+      else e[i] = h0 ? q0 : q1;  // (neither: q1 is the zero it was initialised to)
+      if (h2 && h3) { QIP_KEEP_BRANCH(); e[k] = cadd(q2, q3); }
+      else e[k] = h2 ? q2 : q3;
+    } else {
+      e[i] = tile_row<T, REAL>(g.m[0], g.m[1], h0, h1, a0, a1);
+      e[k] = tile_row<T, REAL>(g.m[2], g.m[3], h2, h3, a0, a1);
+    }
     __builtin_amdgcn_sched_barrier(0);  // one butterfly at a time: interleaving them only costs registers
   }
 }
@@ -1838,7 +1909,7 @@ __device__ __forceinline__ void pass_dense_signs(const TileGate<T>& g, amp_t<T> 
   }
 }
 
-template <typename T, int J, int NE>
+template <typename T, int J, int NE, bool LOOP = false>
 __device__ __forceinline__ void pass_dense(const TileGate<T>& g, amp_t<T> (&e)[NE], const uint32_t (&c)[NE], uint32_t cm) {
   using A = amp_t<T>;
   const bool is_x = (g.b1 & 2u) != 0, real = (g.b1 & 1u) != 0;
@@ -1849,9 +1920,13 @@ __device__ __forceinline__ void pass_dense(const TileGate<T>& g, amp_t<T> (&e)[N
       const int k = i | (1 << J);
       if ((c[i] & cm) != cm) continue;
       QIP_KEEP_BRANCH();
-      const A a0 = e[i];
-      e[i] = e[k];
-      e[k] = a0;
+      if constexpr (LOOP) {
+        cswap_inplace(e[i], e[k]);
+      } else {
+        const A a0 = e[i];
+        e[i] = e[k];
+        e[k] = a0;
+      }
     }
     return;
   }
@@ -1859,11 +1934,11 @@ __device__ __forceinline__ void pass_dense(const TileGate<T>& g, amp_t<T> (&e)[N
     QIP_KEEP_BRANCH();
     pass_dense_signs<T, J, NE>(g, e);
   } else if (cm == 0u && g.nz == 15u) {
-    if (real) pass_dense_body<T, J, true, false, NE>(g, e, c, cm);
-    else pass_dense_body<T, J, false, false, NE>(g, e, c, cm);
+    if (real) pass_dense_body<T, J, true, false, NE, LOOP>(g, e, c, cm);
+    else pass_dense_body<T, J, false, false, NE, LOOP>(g, e, c, cm);
   } else {
-    if (real) pass_dense_body<T, J, true, true, NE>(g, e, c, cm);
-    else pass_dense_body<T, J, false, true, NE>(g, e, c, cm);
+    if (real) pass_dense_body<T, J, true, true, NE, LOOP>(g, e, c, cm);
+    else pass_dense_body<T, J, false, true, NE, LOOP>(g, e, c, cm);
   }
 }
 
@@ -1890,19 +1965,23 @@ __device__ __forceinline__ void pass_dense_lane(const TileGate<T>& g, amp_t<T> (
 
 // e[i] <- f * e[i] for the elements whose pass-bit controls are 1 (HALF >= 0: only elements with pass bit J equal
 // to HALF); straight-line when the gate has no control on a pass bit
-template <typename T, int J, int HALF, int NE>
+template <typename T, int J, int HALF, int NE, bool INPLACE = false>
 __device__ __forceinline__ void pass_scale(amp_t<T> f, amp_t<T> (&e)[NE], const uint32_t (&c)[NE], uint32_t cm) {
   if (cm == 0u) {
 #pragma unroll
     for (int i = 0; i < NE; ++i)
-      if (HALF < 0 || ((i >> J) & 1) == HALF) e[i] = cmul(f, e[i]);
+      if (HALF < 0 || ((i >> J) & 1) == HALF) {
+        if constexpr (INPLACE) cscale_inplace(f, e[i]);
+        else e[i] = cmul(f, e[i]);
+      }
   } else {
     QIP_KEEP_BRANCH();
 #pragma unroll
     for (int i = 0; i < NE; ++i)
       if ((HALF < 0 || ((i >> J) & 1) == HALF) && (c[i] & cm) == cm) {
         QIP_KEEP_BRANCH();
-        e[i] = cmul(f, e[i]);
+        if constexpr (INPLACE) cscale_inplace(f, e[i]);
+        else e[i] = cmul(f, e[i]);
       }
   }
 }
@@ -1910,7 +1989,7 @@ __device__ __forceinline__ void pass_scale(amp_t<T> f, amp_t<T> (&e)[NE], const 
 // diagonal 1-qubit gate whose target is pass bit J: the factor of element i is m[(i >> J) & 1], known at
 // compile time; unit factors (wave-uniform test) leave their four elements untouched.  With lane-bit controls
 // the lanes whose controls are 0 multiply by (1, 0) instead: x*1 - y*0 == x for finite amplitudes.
-template <typename T, int J, int NE>
+template <typename T, int J, int NE, bool INPLACE = false>
 __device__ __forceinline__ void pass_diag(const TileGate<T>& g, amp_t<T> (&e)[NE], const uint32_t (&c)[NE], uint32_t cm,
                                           bool lane_ctl, bool lane_ok) {
   using A = amp_t<T>;
@@ -1924,12 +2003,12 @@ __device__ __forceinline__ void pass_diag(const TileGate<T>& g, amp_t<T> (&e)[NE
       f.x = lane_ok ? f.x : (T)1;
       f.y = lane_ok ? f.y : (T)0;
     }
-    if (half == 0) pass_scale<T, J, 0, NE>(f, e, c, cm);
-    else pass_scale<T, J, 1, NE>(f, e, c, cm);
+    if (half == 0) pass_scale<T, J, 0, NE, INPLACE>(f, e, c, cm);
+    else pass_scale<T, J, 1, NE, INPLACE>(f, e, c, cm);
   }
 }
 
-template <typename T, int J0, int J1, int NE>
+template <typename T, int J0, int J1, int NE, bool LOOP = false>
 __device__ __forceinline__ void pass_swap(amp_t<T> (&e)[NE], const uint32_t (&c)[NE], uint32_t cm, bool lane_ctl, bool lane_ok) {
   using A = amp_t<T>;
 #pragma unroll
@@ -1943,6 +2022,8 @@ __device__ __forceinline__ void pass_swap(amp_t<T> (&e)[NE], const uint32_t (&c)
       QIP_KEEP_BRANCH();
       e[i] = tile_sel(lane_ok, b, a);
       e[k] = tile_sel(lane_ok, a, b);
+    } else if constexpr (LOOP) {
+      cswap_inplace(e[i], e[k]);
     } else {
       e[i] = b;
       e[k] = a;
@@ -2014,6 +2095,11 @@ __device__ __forceinline__ void pass_dense3(const amp_t<T>* __restrict__ M, amp_
 // hide it; left alone the compiler spent 170 registers (VGPR + AGPR) on scheduling freedom = 2 blocks per CU.
 // (f32: the same bound holds without spills once the SLP vectorizer is off — rustqip_amd/build.py; with it the pass
 // packs f32 products into v_pk_* pairs and the kernel needs 180 registers.)
+// EVERY BRANCH IN THIS KERNEL AND IN THE pass_* BODIES IT CALLS IS WAVE-UNIFORM, and must stay so: the unit that instantiates it
+// (qip_tile_interp.hip) is compiled with uniform regions left unstructured (rustqip_amd/build.py, UNIT_FLAGS).  A per-lane
+// condition is a select (tile_sel, a factor of (1, 0)), never an `if`: a lane-dependent branch would still be compiled
+// correctly (the compiler structurizes divergent regions whatever the option says), but it brings the second register set and
+// its latch copies back for every gate.
 template <typename T, bool NT, bool FOLD = false>
 __global__ __launch_bounds__(kTileBlock, 5) void k_tile_passes(amp_t<T>* __restrict__ st, Ins ins, TilePassDesc d,
                                                                               const TileGate<T>* __restrict__ gates,
@@ -2126,7 +2212,7 @@ __global__ __launch_bounds__(kTileBlock, 5) void k_tile_passes(amp_t<T>* __restr
           const A f = ((base >> g.tpos_out) & 1ull) ? g.m[1] : g.m[0];
           if (f.x == (T)1 && f.y == (T)0) break;  // unit entries leave the amplitude untouched
           QIP_KEEP_BRANCH();
-          pass_scale<T, 0, -1>(f, e, c, cm_reg);
+          pass_scale<T, 0, -1, 8, true>(f, e, c, cm_reg);
           break;
         }
         case TOP_DIAG_LANE:
@@ -2142,15 +2228,15 @@ __global__ __launch_bounds__(kTileBlock, 5) void k_tile_passes(amp_t<T>* __restr
             f.x = lane_ok ? f.x : (T)1;
             f.y = lane_ok ? f.y : (T)0;
           }
-          pass_scale<T, 0, -1>(f, e, c, cm_reg);
+          pass_scale<T, 0, -1, 8, true>(f, e, c, cm_reg);
           break;
         }
-        case TOP_DIAG_REG0: pass_diag<T, 0>(g, e, c, cm_reg, g.cm_lane != 0u, (tb & g.cm_lane) == g.cm_lane); break;
-        case TOP_DIAG_REG1: pass_diag<T, 1>(g, e, c, cm_reg, g.cm_lane != 0u, (tb & g.cm_lane) == g.cm_lane); break;
-        case TOP_DIAG_REG2: pass_diag<T, 2>(g, e, c, cm_reg, g.cm_lane != 0u, (tb & g.cm_lane) == g.cm_lane); break;
-        case TOP_DENSE0: pass_dense<T, 0>(g, e, c, cm_reg); break;
-        case TOP_DENSE1: pass_dense<T, 1>(g, e, c, cm_reg); break;
-        case TOP_DENSE2: pass_dense<T, 2>(g, e, c, cm_reg); break;
+        case TOP_DIAG_REG0: pass_diag<T, 0, 8, true>(g, e, c, cm_reg, g.cm_lane != 0u, (tb & g.cm_lane) == g.cm_lane); break;
+        case TOP_DIAG_REG1: pass_diag<T, 1, 8, true>(g, e, c, cm_reg, g.cm_lane != 0u, (tb & g.cm_lane) == g.cm_lane); break;
+        case TOP_DIAG_REG2: pass_diag<T, 2, 8, true>(g, e, c, cm_reg, g.cm_lane != 0u, (tb & g.cm_lane) == g.cm_lane); break;
+        case TOP_DENSE0: pass_dense<T, 0, 8, true>(g, e, c, cm_reg); break;
+        case TOP_DENSE1: pass_dense<T, 1, 8, true>(g, e, c, cm_reg); break;
+        case TOP_DENSE2: pass_dense<T, 2, 8, true>(g, e, c, cm_reg); break;
         case TOP_DENSE_LANE0: pass_dense_lane<T, 0>(g, e, c, cm_reg, (tb & g.cm_lane) == g.cm_lane); break;
         case TOP_DENSE_LANE1: pass_dense_lane<T, 1>(g, e, c, cm_reg, (tb & g.cm_lane) == g.cm_lane); break;
         case TOP_DENSE_LANE2: pass_dense_lane<T, 2>(g, e, c, cm_reg, (tb & g.cm_lane) == g.cm_lane); break;
@@ -2163,9 +2249,9 @@ __global__ __launch_bounds__(kTileBlock, 5) void k_tile_passes(amp_t<T>* __restr
         case TOP_DENSE2Q_20: QIP_D2Q(2, 0); break;
         case TOP_DENSE2Q_21: QIP_D2Q(2, 1); break;
 #undef QIP_D2Q
-        case TOP_SWAP_01: pass_swap<T, 0, 1>(e, c, cm_reg, g.cm_lane != 0u, (tb & g.cm_lane) == g.cm_lane); break;
-        case TOP_SWAP_02: pass_swap<T, 0, 2>(e, c, cm_reg, g.cm_lane != 0u, (tb & g.cm_lane) == g.cm_lane); break;
-        case TOP_SWAP_12: pass_swap<T, 1, 2>(e, c, cm_reg, g.cm_lane != 0u, (tb & g.cm_lane) == g.cm_lane); break;
+        case TOP_SWAP_01: pass_swap<T, 0, 1, 8, true>(e, c, cm_reg, g.cm_lane != 0u, (tb & g.cm_lane) == g.cm_lane); break;
+        case TOP_SWAP_02: pass_swap<T, 0, 2, 8, true>(e, c, cm_reg, g.cm_lane != 0u, (tb & g.cm_lane) == g.cm_lane); break;
+        case TOP_SWAP_12: pass_swap<T, 1, 2, 8, true>(e, c, cm_reg, g.cm_lane != 0u, (tb & g.cm_lane) == g.cm_lane); break;
 #define QIP_D3Q(JA, JB, JC) pass_dense3<T, JA, JB, JC>(mats + 16u * g.nz, e, g.cm_lane != 0u, (tb & g.cm_lane) == g.cm_lane)
         case TOP_DENSE3Q_012: QIP_D3Q(0, 1, 2); break;
         case TOP_DENSE3Q_021: QIP_D3Q(0, 2, 1); break;

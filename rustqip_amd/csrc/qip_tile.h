@@ -114,6 +114,11 @@ template <typename T> struct TileInterpPlan {
 };
 template <typename T> void tile_merge_diag_runs(const TileSegmentPlan<T>& plan, TileInterpPlan<T>* out, uint32_t min_run = 2);
 extern int64_t g_tile_diag_runs;  // global option "tile_diag_runs" (1 = on)
+// qip_tile_interp.hip: one k_tile_passes launch (`fold` non-null: the sweep stores packed into `out`); errors via hipGetLastError
+template <typename T>
+void launch_tile_passes(hipStream_t stream, dim3 grid, size_t lds, bool nt, amp_t<T>* st, const Ins& ins, const TilePassDesc& pd,
+                        const TileGate<T>* gates, const amp_t<T>* mats, amp_t<T>* out, const TileStorePerm* fold,
+                        const TileDiagItem<T>* items);
 
 // A segment's item list with its uncontrolled X gates absorbed (INTERPRETER launches only, like the diagonal runs: plans, the
 // generators, the one-op sweeps and the wide path never see it).  Every X target of a segment is a tile position, so X is a fixed

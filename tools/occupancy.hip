@@ -1,5 +1,9 @@
 // Occupancy the runtime computes for the tile-sweep kernels (blocks per CU), and device limits.
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I include tools/occupancy.hip -o tools/occupancy
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -mllvm -structurizecfg-skip-uniform-regions \
+//         -I include tools/occupancy.hip -o tools/occupancy
+// (the options of rustqip_amd/build.py for the unit that holds k_tile_passes, qip_tile_interp: without the -mllvm option the
+// k_tile_passes built here is not the library's.  k_tile_gates is built WITHOUT it in the library (qip_circuit); its registers
+// here may differ by a few, its LDS-bound blocks per CU do not.)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include "../rustqip_amd/csrc/qip_kernels.h"
