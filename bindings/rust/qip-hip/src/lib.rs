@@ -22,6 +22,7 @@ pub mod op;
 pub mod replay;
 pub mod state;
 pub mod sys;
+pub mod sys_ext;
 
 pub use builder::{HipBuilder, HipMeasurementHandle, HipMeasurements, HipStochasticMeasurementHandle};
 pub use iterators::HipElement;

@@ -1,6 +1,7 @@
 //! `HipState`: the device-resident `2^n` amplitude vector (`state` + `arena` of `builder.rs:406-407`).
 use crate::op::{marshal, HipPrecision};
 use crate::sys;
+use crate::sys_ext;
 use num_complex::Complex;
 use qip_iterators::iterators::MatrixOp;
 use std::ffi::{CStr, CString};
@@ -119,6 +120,16 @@ impl<P: HipPrecision> HipState<P> {
         let f = forced.map(|v| v as i64).unwrap_or(-1);
         check(unsafe { sys::qip_hip_state_measure(self.h, idx.as_ptr(), idx.len() as u32, f, rand_u01, &mut m, &mut p) })?;
         Ok((m as usize, p))
+    }
+    /// Many samples of the state in one call (`include/qip_hipx.h`, beyond the reference's interface): element `j` is the
+    /// outcome `soft_measure` (measurement_ops.rs:153-176) gives for `rand_u01[j]`, all of them for about the cost of two
+    /// single samples.  The state is not changed.
+    pub fn soft_measure_many(&self, indices: &[u64], rand_u01: &[f64]) -> Result<Vec<u64>, HipError> {
+        let mut out = vec![0u64; rand_u01.len()];
+        check(unsafe {
+            sys_ext::qipx_state_soft_measure_many(self.h, indices.as_ptr(), indices.len() as u32, rand_u01.as_ptr(), rand_u01.len() as u64, out.as_mut_ptr())
+        })?;
+        Ok(out)
     }
     pub fn raw(&mut self) -> *mut sys::qip_hip_state {
         self.h

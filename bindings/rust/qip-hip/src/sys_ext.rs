@@ -1,0 +1,20 @@
+//! Raw bindings of `include/qip_hipx.h`: capabilities beyond the reference's interface (prefix `qipx_`, versioned on their own:
+//! `QIPX_ABI_VERSION`).  `sys.rs` stays the binding contract of `include/qip_hip.h`; `tests/test_hipx_contract_cpu.py` compares
+//! this file with the header.
+use crate::sys::qip_hip_state;
+use std::os::raw::{c_double, c_int};
+
+pub const QIPX_ABI_VERSION: c_int = 1;
+
+extern "C" {
+    pub fn qipx_abi_version() -> c_int;
+    /// `measured[j]` = the outcome of the single-sample call for `rand_u01[j]`, `j < count`; the state is not changed.
+    pub fn qipx_state_soft_measure_many(
+        s: *mut qip_hip_state,
+        indices: *const u64,
+        k: u32,
+        rand_u01: *const c_double,
+        count: u64,
+        measured: *mut u64,
+    ) -> c_int;
+}

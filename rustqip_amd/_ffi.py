@@ -159,6 +159,13 @@ DEBUG_SIGNATURES = {
     "qip_hip_dist_debug_pieces": (_i64, [_int, _int, _u64, _u64, _u64, C.POINTER(C.c_int32), _u64p, _u64p]),
 }
 
+# capabilities beyond the reference's interface (include/qip_hipx.h, node QIP_HIPX: versioned on its own, not part of the
+# binding contract above)
+EXT_SIGNATURES = {
+    "qipx_abi_version": (_int, []),
+    "qipx_state_soft_measure_many": (_int, [_statep, _u64p, _u32, _dblp, _u64, _u64p]),
+}
+
 
 def _load() -> C.CDLL:
     if not os.path.exists(LIB_PATH):
@@ -167,7 +174,7 @@ def _load() -> C.CDLL:
             "(hipcc --offload-arch=gfx950). rustqip_amd has no CPU fallback."
         )
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

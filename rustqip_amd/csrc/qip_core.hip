@@ -463,6 +463,7 @@ extern "C" int qip_hip_state_destroy(qip_hip_state* s) try {
   if (s->arena) (void)hipFree(s->arena);
   if (s->d_partial) (void)hipFree(s->d_partial);
   if (s->d_ticket) (void)hipFree(s->d_ticket);
+  if (s->d_sample) (void)hipFree(s->d_sample);
   if (s->owns_stream && s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
   return QIP_OK;
@@ -567,6 +568,10 @@ extern "C" int qip_hip_state_set_option(qip_hip_state* s, const char* key, int64
   else if (!strcmp(key, "tile_wide")) s->tile_wide = value;
   else if (!strcmp(key, "tile_auto")) s->tile_auto = value;
   else if (!strcmp(key, "pair_floor")) s->pair_floor = value;
+  else if (!strcmp(key, "sample_slab")) {
+    if (value < 1) return fail(QIP_ERR_INVALID, "sample_slab is at least 1");
+    s->sample_slab = value;
+  }
 #ifdef QIP_HIP_TUNING
   else if (!strcmp(key, "lowbit_shuffle")) s->lowbit_shuffle = value;
   else if (!strcmp(key, "packed_f32")) s->packed_f32 = value;

@@ -163,6 +163,10 @@ struct qip_hip_state {
   double* d_partial = nullptr;
   void* d_ticket = nullptr;  // soft_measure in one launch: ticket counter + result words (qip_measure.hip)
   size_t partial_cap = 0;
+  // qipx_state_soft_measure_many (qip_measure.hip): per-sample remainders, outcomes, candidate chunks and sample lists of one slab
+  void* d_sample = nullptr;
+  size_t sample_cap = 0;            // samples the scratch holds
+  int64_t sample_slab = 1ll << 22;  // option "sample_slab": samples per slab
   // options
   int64_t force_generic = 0;
   int64_t profile = 0;

@@ -2903,17 +2903,101 @@ __global__ __launch_bounds__(kBlock) void k_gather_indices(const amp_t<T>* __res
 // loads of one lane at n = 30, most of soft_measure's time beyond the norm pass).  A (sub-)segment that came close without
 // crossing hands its exact remainder on.  *r_io / *found live in shared memory, set by the caller (found = ~0).
 __device__ __forceinline__ int walk_sums(const double* v, int start, int cnt, double& r) {
-  for (int t = start; t < cnt; ++t) {
-    if (r - v[t] <= 1e-9 * (1.0 + v[t])) return t;  // may cross (or come within rounding of it): look inside
+  // Eight sums at a time: the loads and the margins do not depend on r, so only the eight subtractions are a chain; the walk
+  // stops at the FIRST sum that may cross, with r as it stood before that sum — the one-at-a-time loop below, sum for sum.
+  constexpr int W = 8;
+  int t = start;
+  for (; t + W <= cnt; t += W) {
+    double x[W], before[W];
+    bool may[W];
+#pragma unroll
+    for (int u = 0; u < W; ++u) x[u] = v[t + u];
+    double rr = r;
+#pragma unroll
+    for (int u = 0; u < W; ++u) {
+      before[u] = rr;
+      rr = rr - x[u];
+      may[u] = rr <= 1e-9 * (1.0 + x[u]);  // may cross (or come within rounding of it): look inside
+    }
+    int first = -1;
+#pragma unroll
+    for (int u = W - 1; u >= 0; --u) first = may[u] ? u : first;
+    if (first >= 0) {
+#pragma unroll
+      for (int u = 0; u < W; ++u)
+        if (u == first) r = before[u];
+      return t + first;
+    }
+    r = rr;
+  }
+  for (; t < cnt; ++t) {
+    if (r - v[t] <= 1e-9 * (1.0 + v[t])) return t;
     r -= v[t];
   }
   return -1;
 }
 
+// The crossing search in two parts, shared by the single call's kernels (k_find_crossing, k_chunk_norms_cross) and by the
+// batched one (k_resolve_many): every sample that lands in a chunk walks the SAME 256 segment sums, so the batch forms them
+// once per block and resolves its samples one after the other with the code the single call runs.
+// Part 1: seg_sum[sg] = sum |amp|^2 over segment sg of the chunk [lo, lo + len), in double.  Ends with a barrier.
 template <typename T>
-__device__ void find_crossing_block(const amp_t<T>* __restrict__ st, uint64_t lo, uint64_t len, double* r_io,
-                                    unsigned long long* found) {
-  __shared__ double seg_sum[kBlock], sub_sum[kBlock];
+__device__ __forceinline__ void chunk_segment_sums(const amp_t<T>* __restrict__ st, uint64_t lo, uint64_t len, double* seg_sum) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63u;
+  const uint64_t end = lo + len;
+  const uint64_t seg = (len + kBlock - 1) / kBlock;
+  // the 256 segment sums, a wave per segment: 64 lanes read consecutive amplitudes (one lane per segment would touch 64
+  // different lines per load instruction — measured: the larger part of the crossing search's time).  A wave takes two segments
+  // at a time and reads four elements of each before it adds them, so eight loads are in flight; every lane still adds its
+  // elements one after the other in index order, so the sums are those of the plain loop.
+  auto prob = [](amp_t<T> x) { return (double)(x.x * x.x + x.y * x.y); };
+  for (uint32_t s0 = tid >> 6; s0 < (uint32_t)kBlock; s0 += 2 * (kBlock / 64)) {
+    uint64_t i[2], b[2];
+    uint32_t sg[2];
+    double acc[2] = {0, 0};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      sg[h] = s0 + h * (kBlock / 64);
+      const uint64_t a = lo + (uint64_t)sg[h] * seg < end ? lo + (uint64_t)sg[h] * seg : end;
+      b[h] = a + seg < end ? a + seg : end;
+      i[h] = a + lane;
+    }
+    while (i[0] + 192 < b[0] && i[1] + 192 < b[1]) {
+      amp_t<T> x[2][4];
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) x[h][u] = st[i[h] + 64 * u];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc[h] += prob(x[h][u]);
+        i[h] += 256;
+      }
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+      for (; i[h] < b[h]; i[h] += 64) acc[h] += prob(st[i[h]]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      acc[0] += __shfl_down(acc[0], o, 64);
+      acc[1] += __shfl_down(acc[1], o, 64);
+    }
+    if (lane == 0) {
+      seg_sum[sg[0]] = acc[0];
+      seg_sum[sg[1]] = acc[1];
+    }
+  }
+  __syncthreads();
+}
+
+// Part 2: one remainder *r_io against the segment sums of part 1 (block-wide; *r_io / *found in shared memory, *found = ~0 on
+// entry, both visible to the block).  On return either *found is the crossing index, or the chunk never crosses and *r_io is
+// the remainder after it.  The caller puts a barrier before it reads them.
+template <typename T>
+__device__ void resolve_crossing(const amp_t<T>* __restrict__ st, uint64_t lo, uint64_t len, const double* seg_sum, double* r_io,
+                                 unsigned long long* found) {
+  __shared__ double sub_sum[kBlock];
   __shared__ int owner, owner2;
   const uint32_t tid = threadIdx.x;
   const uint64_t end = lo + len;
@@ -2926,21 +3010,6 @@ __device__ void find_crossing_block(const amp_t<T>* __restrict__ st, uint64_t lo
     return acc;
   };
   const uint64_t seg = (len + kBlock - 1) / kBlock;
-  // the 256 segment sums, a wave per segment in turn: 64 lanes read consecutive amplitudes (one lane per segment would touch 64
-  // different lines per load instruction — measured: the larger part of the crossing search's time)
-  for (uint32_t sg = tid >> 6; sg < (uint32_t)kBlock; sg += kBlock / 64) {
-    const uint64_t a = lo + (uint64_t)sg * seg < end ? lo + (uint64_t)sg * seg : end;
-    const uint64_t b = a + seg < end ? a + seg : end;
-    double acc = 0;
-    for (uint64_t i = a + (tid & 63u); i < b; i += 64) {
-      const amp_t<T> x = st[i];
-      acc += (double)(x.x * x.x + x.y * x.y);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-    if ((tid & 63u) == 0) seg_sum[sg] = acc;
-  }
-  __syncthreads();
   int start = 0;
   while (true) {
     if (tid == 0) {
@@ -2988,6 +3057,14 @@ __device__ void find_crossing_block(const amp_t<T>* __restrict__ st, uint64_t lo
     start = own + 1;
     __syncthreads();
   }
+}
+
+template <typename T>
+__device__ void find_crossing_block(const amp_t<T>* __restrict__ st, uint64_t lo, uint64_t len, double* r_io,
+                                    unsigned long long* found) {
+  __shared__ double seg_sum[kBlock];
+  chunk_segment_sums<T>(st, lo, len, seg_sum);
+  resolve_crossing<T>(st, lo, len, seg_sum, r_io, found);
 }
 
 // result[0] = index (or ~0 when the chunk never crosses), result[1] = bits of the remaining r (double).
@@ -3117,6 +3194,146 @@ __global__ __launch_bounds__(kBlock) void k_chunk_norms_cross(const E* __restric
     result[0] = found_at;
     result[1] = (uint64_t)__double_as_longlong(r_cur);
     *counter = 0u;  // ready for the next launch (stream order; the handle's own allocation, zeroed when made)
+  }
+}
+
+// ---- many samples of one state (qipx_state_soft_measure_many) -----------------------------------------------------------
+// Every sample is the single call's function of (state, sample): the host walk over the chunk sums runs here one lane per
+// sample (k_walk_chunks), the samples are grouped by candidate chunk on the host, and one block per group of at most
+// kSampleShotsPerBlock samples runs the single call's crossing search in that chunk (k_resolve_many).
+constexpr uint32_t kSampleNone = 0xffffffffu;  // candidate chunk: the walk ran off the end (the sample never crosses)
+constexpr uint32_t kSampleDone = 0xfffffffeu;  // ... : the crossing was found, the outcome is written
+// Samples per block: a crowded chunk gets several blocks (re-reading <= 1 MiB from cache is cheap, a block's samples are resolved
+// one after the other); with more samples than kSampleBlocksWanted blocks of 8 would hold, the blocks grow instead of multiplying.
+constexpr uint32_t kSampleShotsPerBlock = 8, kSampleShotsPerBlockMax = 64, kSampleBlocksWanted = 16384;
+constexpr int kWalkTile = 1024;                // chunk sums staged per step of the walk
+
+// The host loop of soft_measure_t over the chunk sums, for many samples: the very subtractions, in double, in chunk order, with
+// the same margin — NOT a prefix sum + search (r - s0 - s1 - ... rounds differently from r - (s0 + s1 + ...)).  All lanes of a
+// block read the same sum at the same step: the sums pass through LDS a tile at a time.
+// list == nullptr: the first round, sample i starts at chunk 0 with r = its sample (rounded to the state's precision first);
+// otherwise sample list[i] goes on from the chunk after the one it did not cross in, with the remainder that chunk left.
+// A chunk whose sum is exactly 0 holds no non-zero product: with r > 0 nothing in it can cross and the search inside it hands r
+// back after a round trip through T — the walk passes it whenever that round trip is the identity.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_walk_chunks(const double* __restrict__ sums, uint32_t nchunks,
+                                                        const uint32_t* __restrict__ list, uint32_t nshots,
+                                                        double* __restrict__ r_io, uint32_t* __restrict__ cand) {
+  __shared__ double tile[kWalkTile], margin[kWalkTile];
+  __shared__ int open_lanes;
+  constexpr int W = 8;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t i = blockIdx.x * kBlock + tid;
+  const bool active = i < nshots;
+  const uint32_t shot = active ? (list ? list[i] : i) : 0u;
+  const uint32_t start = active ? (list ? cand[shot] + 1u : 0u) : nchunks;
+  double r = active ? r_io[shot] : 0.0;
+  if (!list) r = (double)(T)r;
+  uint32_t found = kSampleNone;
+  bool done = start >= nchunks;
+  // one sum: does the walk stop here?  (rr: the remainder before it, d = rr - v)
+  auto stops = [](double v, double m, double rr, double d) {
+    const bool passed = v == 0.0 && rr > 0.0 && (double)(T)rr == rr;  // an empty chunk: nothing in it can cross, r comes back as it is
+    return !(d > m) && !passed;  // not clearly past this chunk: it may cross (or come within rounding of it): look inside
+  };
+  for (uint32_t base = 0; base < nchunks; base += kWalkTile) {
+    if (tid == 0) open_lanes = 0;
+    __syncthreads();  // (also: every lane has left the previous tile)
+    if (!done) open_lanes = 1;
+    __syncthreads();
+    if (!open_lanes) break;
+    const uint32_t cnt = nchunks - base < (uint32_t)kWalkTile ? nchunks - base : (uint32_t)kWalkTile;
+    for (uint32_t t = tid; t < cnt; t += kBlock) {
+      const double v = sums[base + t];
+      tile[t] = v;
+      margin[t] = 1e-9 * (1.0 + v);
+    }
+    __syncthreads();
+    if (done) continue;
+    uint32_t t = start > base ? start - base : 0u;
+    // eight sums at a time: only the subtractions are a chain (r - v IS the next r when the walk goes on); the walk stops at
+    // the first sum that stops it, with r as it stood before that sum
+    for (; t + W <= cnt && !done; t += W) {
+      double before[W];
+      bool stop[W];
+      double rr = r;
+#pragma unroll
+      for (int u = 0; u < W; ++u) {
+        const double v = tile[t + u], d = rr - v;
+        before[u] = rr;
+        stop[u] = stops(v, margin[t + u], rr, d);
+        rr = d;
+      }
+      int first = -1;
+#pragma unroll
+      for (int u = W - 1; u >= 0; --u) first = stop[u] ? u : first;
+      if (first >= 0) {
+#pragma unroll
+        for (int u = 0; u < W; ++u)
+          if (u == first) r = before[u];
+        found = base + t + (uint32_t)first;
+        done = true;
+      } else {
+        r = rr;
+      }
+    }
+    for (; t < cnt && !done; ++t) {
+      const double v = tile[t], d = r - v;
+      if (stops(v, margin[t], r, d)) {
+        found = base + t;
+        done = true;
+      } else {
+        r = d;
+      }
+    }
+  }
+  if (active) {
+    cand[shot] = found;
+    r_io[shot] = r;
+  }
+}
+
+struct SampleBlock {
+  uint32_t chunk, first, count;  // the samples order[first .. first + count) have `chunk` as their candidate
+};
+
+// One block per SampleBlock: the chunk's segment sums once, then every sample of the block through resolve_crossing.  A sample
+// that crosses gets its outcome (the measured bits of the crossing index) and cand = kSampleDone; one that does not keeps its
+// candidate, gets the exact remainder after the chunk and counts in *n_open (it goes round again from the next chunk).
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_resolve_many(const amp_t<T>* __restrict__ st, uint64_t namps, uint64_t chunk,
+                                                         const SampleBlock* __restrict__ blocks, const uint32_t* __restrict__ order,
+                                                         double* __restrict__ r_io, uint32_t* __restrict__ cand,
+                                                         uint64_t* __restrict__ out, MeasDesc md, unsigned int* __restrict__ n_open) {
+  __shared__ double seg_sum[kBlock];
+  __shared__ double r_cur;
+  __shared__ unsigned long long found_at;
+  const SampleBlock b = blocks[blockIdx.x];
+  const uint64_t lo = (uint64_t)b.chunk * chunk;
+  const uint64_t len = lo + chunk < namps ? chunk : namps - lo;
+  chunk_segment_sums<T>(st, lo, len, seg_sum);
+  for (uint32_t j = 0; j < b.count; ++j) {
+    const uint32_t shot = order[b.first + j];
+    if (threadIdx.x == 0) {
+      r_cur = r_io[shot];
+      found_at = ~0ull;
+    }
+    __syncthreads();
+    resolve_crossing<T>(st, lo, len, seg_sum, &r_cur, &found_at);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const unsigned long long at = found_at;
+      if (at != ~0ull) {
+        uint64_t m = 0;
+        for (uint32_t q = 0; q < md.k; ++q) m |= ((at >> md.mpos[q]) & 1ull) << q;
+        out[shot] = m;
+        cand[shot] = kSampleDone;
+      } else {
+        r_io[shot] = r_cur;
+        atomicAdd(n_open, 1u);
+      }
+    }
+    __syncthreads();
   }
 }
 

@@ -1,5 +1,6 @@
 // qip_measure.hip — measurement on the device (qip/src/state_ops/measurement_ops.rs).
 #include "qip_internal.h"
+#include "../../include/qip_hipx.h"
 
 // ---------------------------------------------------------------------------------------
 // measurement
@@ -424,6 +425,138 @@ extern "C" int qip_hip_state_soft_measure(qip_hip_state* s, const uint64_t* indi
   QCHK(check_measure_indices(s, indices, k, &md, &pos));
   return s->dtype == QIP_C64 ? soft_measure_t<double>(s, md, rand_u01, measured)
                              : soft_measure_t<float>(s, md, rand_u01, measured);
+} QIP_CATCH_ALL
+
+// ---- many samples of one state: capabilities beyond the reference's interface (include/qip_hipx.h) --------------------
+// measured[j] = what soft_measure_t (two-launch form) gives for rand_u01[j]: one norm pass, then per slab of samples
+//   walk    k_walk_chunks: the host loop above, one lane per sample -> (candidate chunk or none, remainder)
+//   group   the samples sorted by candidate chunk (a counting sort on the host), a few (kSampleShotsPerBlock) per block
+//   resolve k_resolve_many: k_find_crossing's search, the chunk's segment sums formed once per block
+//   rounds  the samples that came close to a chunk without crossing in it go on from the next chunk with their exact remainder,
+//           as the host loop does after a k_find_crossing that found nothing; every round moves each of them on by >= 1 chunk.
+// The scratch belongs to the handle (d_sample), grown on demand, sized by the slab, never allocated per round.
+extern "C" int qipx_abi_version(void) { return QIPX_ABI_VERSION; }
+
+namespace {
+constexpr uint64_t kSampleSlabMax = 1ull << 28;  // sample numbers are 32-bit on the device
+struct SampleScratch {
+  unsigned int* n_open;
+  double* r;
+  uint64_t* out;
+  uint32_t *cand, *list, *order;
+  SampleBlock* blocks;
+};
+}  // namespace
+
+static int ensure_sample(qip_hip_state* s, size_t shots, SampleScratch* sc) {
+  if (shots > s->sample_cap) {
+    if (s->d_sample) {
+      HIPCHK(hipStreamSynchronize(s->stream));
+      HIPCHK(hipFree(s->d_sample));
+      s->d_sample = nullptr;
+      s->sample_cap = 0;
+    }
+    const size_t cap = std::max<size_t>(shots, 4096);
+    HIPCHK(hipMalloc(&s->d_sample, 16 + cap * (8 + 8 + 4 + 4 + 4 + sizeof(SampleBlock))));
+    s->sample_cap = cap;
+  }
+  const size_t cap = s->sample_cap;
+  char* p = (char*)s->d_sample;
+  sc->n_open = (unsigned int*)p;
+  sc->r = (double*)(p + 16);
+  sc->out = (uint64_t*)(p + 16 + cap * 8);
+  sc->cand = (uint32_t*)(p + 16 + cap * 16);
+  sc->list = sc->cand + cap;
+  sc->order = sc->list + cap;
+  sc->blocks = (SampleBlock*)(sc->order + cap);  // (a block holds at least one sample: never more blocks than samples)
+  return QIP_OK;
+}
+
+template <typename T>
+static int soft_measure_many_t(qip_hip_state* s, const MeasDesc& md, const double* rand_u01, uint64_t count, uint64_t* measured) {
+  std::vector<double> sums;
+  uint64_t chunk = 0;
+  QCHK(chunk_norms<T>(s, &chunk, &sums, kSoftMeasureChunks));  // the chunk sums stay in d_partial: nothing below touches it
+  const uint32_t nchunks = (uint32_t)sums.size();
+  const uint64_t slab = std::min<uint64_t>({(uint64_t)s->sample_slab, kSampleSlabMax, count});
+  SampleScratch sc;
+  QCHK(ensure_sample(s, (size_t)slab, &sc));
+  const amp_t<T>* amps = (const amp_t<T>*)s->cur;
+  std::vector<uint32_t> cand, act, next, order, fill(nchunks);
+  std::vector<SampleBlock> blocks;
+  for (uint64_t done = 0; done < count; done += slab) {
+    const uint32_t m = (uint32_t)std::min<uint64_t>(slab, count - done);
+    HIPCHK(hipMemcpyAsync(sc.r, rand_u01 + done, (size_t)m * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    HIPCHK(hipMemsetAsync(sc.out, 0, (size_t)m * sizeof(uint64_t), s->stream));  // never crossing: amplitude index 0 (:166)
+    cand.resize(m);
+    act.resize(m);
+    for (uint32_t i = 0; i < m; ++i) act[i] = i;
+    for (bool first = true; !act.empty(); first = false) {
+      const uint32_t na = (uint32_t)act.size();
+      if (!first) HIPCHK(hipMemcpyAsync(sc.list, act.data(), (size_t)na * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+      hipLaunchKernelGGL((k_walk_chunks<T>), dim3(grid_for(na, kBlock)), dim3(kBlock), 0, s->stream, (const double*)s->d_partial,
+                         nchunks, first ? (const uint32_t*)nullptr : (const uint32_t*)sc.list, na, sc.r, sc.cand);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(cand.data(), sc.cand, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+      HIPCHK(hipStreamSynchronize(s->stream));
+      // group the round's samples by candidate chunk
+      std::fill(fill.begin(), fill.end(), 0u);
+      uint32_t landed = 0;
+      for (uint32_t shot : act) {
+        const uint32_t c = cand[shot];
+        if (c == kSampleNone) continue;
+        if (c >= nchunks) return fail(QIP_ERR_DEVICE, "soft_measure_many: the walk named chunk %u of %u", c, nchunks);
+        fill[c] += 1;
+        landed += 1;
+      }
+      if (landed == 0) break;
+      blocks.clear();
+      const uint32_t per_block = std::min(std::max(landed / kSampleBlocksWanted, kSampleShotsPerBlock), kSampleShotsPerBlockMax);
+      uint32_t at = 0;
+      for (uint32_t c = 0; c < nchunks; ++c) {
+        const uint32_t n_c = fill[c];
+        for (uint32_t f = 0; f < n_c; f += per_block)
+          blocks.push_back(SampleBlock{c, at + f, std::min<uint32_t>(per_block, n_c - f)});
+        fill[c] = at;  // from here on: where the chunk's next sample goes
+        at += n_c;
+      }
+      order.resize(landed);
+      for (uint32_t shot : act)
+        if (cand[shot] != kSampleNone) order[fill[cand[shot]]++] = shot;
+      HIPCHK(hipMemcpyAsync(sc.order, order.data(), (size_t)landed * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+      HIPCHK(hipMemcpyAsync(sc.blocks, blocks.data(), blocks.size() * sizeof(SampleBlock), hipMemcpyHostToDevice, s->stream));
+      HIPCHK(hipMemsetAsync(sc.n_open, 0, sizeof(unsigned int), s->stream));
+      hipLaunchKernelGGL((k_resolve_many<T>), dim3((unsigned)blocks.size()), dim3(kBlock), 0, s->stream, amps, s->namps, chunk,
+                         (const SampleBlock*)sc.blocks, (const uint32_t*)sc.order, sc.r, sc.cand, sc.out, md, sc.n_open);
+      HIPCHK(hipGetLastError());
+      unsigned int n_open = 0;
+      HIPCHK(hipMemcpyAsync(&n_open, sc.n_open, sizeof n_open, hipMemcpyDeviceToHost, s->stream));
+      HIPCHK(hipStreamSynchronize(s->stream));
+      if (n_open == 0) break;
+      // the samples that did not cross in their candidate chunk (it is still their `cand`) go round again
+      HIPCHK(hipMemcpyAsync(cand.data(), sc.cand, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+      HIPCHK(hipStreamSynchronize(s->stream));
+      next.clear();
+      for (uint32_t shot : order)
+        if (cand[shot] < nchunks) next.push_back(shot);
+      act.swap(next);
+    }
+    HIPCHK(hipMemcpyAsync(measured + done, sc.out, (size_t)m * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+  }
+  return QIP_OK;
+}
+
+extern "C" int qipx_state_soft_measure_many(qip_hip_state* s, const uint64_t* indices, uint32_t k, const double* rand_u01,
+                                            uint64_t count, uint64_t* measured) try {
+  STATE_ENTER(s);
+  MeasDesc md;
+  std::vector<uint32_t> pos;
+  QCHK(check_measure_indices(s, indices, k, &md, &pos));
+  if (count == 0) return QIP_OK;
+  if (!rand_u01 || !measured) return fail(QIP_ERR_INVALID, "null sample or result array");
+  return s->dtype == QIP_C64 ? soft_measure_many_t<double>(s, md, rand_u01, count, measured)
+                             : soft_measure_many_t<float>(s, md, rand_u01, count, measured);
 } QIP_CATCH_ALL
 
 extern "C" int qip_hip_state_measure(qip_hip_state* s, const uint64_t* indices, uint32_t k,

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "qip_hip.h"
+#include "qip_hipx.h"
 
 namespace qip {
 
@@ -362,6 +363,14 @@ template <typename P> class HipState {
     uint64_t m = 0;
     check(qip_hip_state_soft_measure(h_, idx.data(), (uint32_t)idx.size(), rand_u01, &m));
     return size_t(m);
+  }
+  /// soft_measure for many samples in one call (qip_hipx.h, beyond the reference's interface): element j is
+  /// soft_measure(indices, rand_u01[j]); the state is not changed.
+  std::vector<uint64_t> soft_measure_many(const std::vector<size_t>& indices, const std::vector<double>& rand_u01) const {
+    std::vector<uint64_t> idx(indices.begin(), indices.end());
+    std::vector<uint64_t> out(rand_u01.size());
+    check(qipx_state_soft_measure_many(h_, idx.data(), (uint32_t)idx.size(), rand_u01.data(), rand_u01.size(), out.data()));
+    return out;
   }
   std::vector<double> measure_probs(const std::vector<size_t>& indices) const {
     std::vector<uint64_t> idx(indices.begin(), indices.end());

@@ -176,6 +176,11 @@ def make_op_matrix(n: int, op: MatrixOp, dtype=np.complex128) -> np.ndarray:  # 
     return np.stack(cols, axis=1)
 
 
+def ext_abi_version() -> int:
+    """version of the capabilities beyond the reference's interface (include/qip_hipx.h) the library was built with"""
+    return int(_ffi.lib.qipx_abi_version())
+
+
 def _u64_array(values: Sequence[int]):
     arr = (C.c_uint64 * len(values))(*[int(v) for v in values])
     return arr
@@ -352,6 +357,21 @@ class HipState:
         _check(_ffi.lib.qip_hip_state_soft_measure(self._h, _u64_array(indices), len(indices), float(rand_u01),
                                                    C.byref(out)))
         return int(out.value)
+
+    def soft_measure_many(self, indices: Sequence[int], rand_u01) -> np.ndarray:
+        """uint64[len(rand_u01)]: element j is soft_measure(indices, rand_u01[j]), all of them for about the cost of two
+        single calls (include/qip_hipx.h: one pass for the chunk sums, one read of every chunk a sample lands in)"""
+        rs = np.ascontiguousarray(rand_u01, dtype=np.float64).reshape(-1)
+        out = np.empty(len(rs), dtype=np.uint64)
+        _check(_ffi.lib.qipx_state_soft_measure_many(self._h, _u64_array(indices), len(indices),
+                                                     rs.ctypes.data_as(C.POINTER(C.c_double)), len(rs),
+                                                     out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out
+
+    def sample(self, indices: Sequence[int], shots: int, seed: int) -> np.ndarray:
+        """`shots` outcomes of measuring `indices`, the state left as it is: soft_measure_many over the uniform draws of
+        np.random.Generator(np.random.PCG64(seed))"""
+        return self.soft_measure_many(indices, np.random.Generator(np.random.PCG64(seed)).random(int(shots)))
 
     def measure(self, indices: Sequence[int], measured: Optional[int] = None,
                 rand_u01: float = 0.0) -> Tuple[int, float]:
