@@ -131,6 +131,28 @@ impl<P: HipPrecision> HipState<P> {
         })?;
         Ok(out)
     }
+    /// <psi| P |psi> of Pauli strings (`include/qip_hipx.h`, beyond the reference's interface): a term is a list of
+    /// `(qubit, code)` with code 0 = I, 1 = X, 2 = Y, 3 = Z.  The raw quadratic form (not divided by the norm), in double for
+    /// both precisions; terms that share their X/Y qubits share passes over the vector.  The state is not changed.
+    pub fn expect_pauli(&self, terms: &[Vec<(u64, u8)>]) -> Result<Vec<f64>, HipError> {
+        let mut start = vec![0u64];
+        let (mut qubits, mut paulis) = (Vec::new(), Vec::new());
+        for term in terms {
+            for &(q, p) in term {
+                qubits.push(q);
+                paulis.push(p);
+            }
+            start.push(qubits.len() as u64);
+        }
+        // (never a dangling-but-null pointer question on the C side: the arrays hold at least one element)
+        qubits.push(0);
+        paulis.push(0);
+        let mut out = vec![0f64; terms.len()];
+        check(unsafe {
+            sys_ext::qipx_state_expect_pauli(self.h, start.as_ptr(), qubits.as_ptr(), paulis.as_ptr(), terms.len() as u64, out.as_mut_ptr())
+        })?;
+        Ok(out)
+    }
     pub fn raw(&mut self) -> *mut sys::qip_hip_state {
         self.h
     }

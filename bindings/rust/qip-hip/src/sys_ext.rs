@@ -17,4 +17,24 @@ extern "C" {
         count: u64,
         measured: *mut u64,
     ) -> c_int;
+    /// `values[t]` = <psi| P_t |psi>, `t < count`: term `t` is the product of `paulis[i]` (0 = I, 1 = X, 2 = Y, 3 = Z) on qubit
+    /// `qubits[i]` for `term_start[t] <= i < term_start[t+1]`; the raw quadratic form, the state is not changed.
+    pub fn qipx_state_expect_pauli(
+        s: *mut qip_hip_state,
+        term_start: *const u64,
+        qubits: *const u64,
+        paulis: *const u8,
+        count: u64,
+        values: *mut c_double,
+    ) -> c_int;
+    /// Host only: the passes over the vector the call above makes when at most `group` terms share one (0 = the default).
+    pub fn qipx_expect_pauli_passes(
+        n: u32,
+        term_start: *const u64,
+        qubits: *const u64,
+        paulis: *const u8,
+        count: u64,
+        group: u32,
+        passes: *mut u64,
+    ) -> c_int;
 }

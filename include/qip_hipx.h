@@ -40,6 +40,51 @@ int qipx_abi_version(void);
 int qipx_state_soft_measure_many(qip_hip_state* s, const uint64_t* indices, uint32_t k,
                                  const double* rand_u01, uint64_t count, uint64_t* measured);
 
+/* Expectation values of Pauli strings.  (Added without a change of QIPX_ABI_VERSION: the addition is purely additive, every
+ * earlier declaration is as it was.)
+ *
+ * values[t] = <psi| P_t |psi>, t < count.  Term t is the product of paulis[i] (0 = I, 1 = X, 2 = Y, 3 = Z) on qubit
+ * qubits[i] for term_start[t] <= i < term_start[t+1]; qubit q is index bit n-1-q as everywhere in qip_hip.h.
+ *
+ * The value.  With x = the index bits under X or Y, z = those under Z or Y and n_Y the number of Y factors,
+ *   values[t] = sum_j conj(psi[j ^ x]) * i^n_Y * (-1)^popcount(j & z) * psi[j],
+ * the raw quadratic form: it is NOT divided by the norm, so an unnormalised state gives norm^2 times the value of the
+ * normalised one.  An empty term (term_start[t] == term_start[t+1]), and a term made of I factors only, gives sum |psi_j|^2.
+ *
+ * Precision.  Products and sums are formed in double for Complex<f64> and for Complex<f32> states alike; f32 amplitudes are
+ * widened before the first product.  (qip_hip.h's norm_sqr and measure_probs form |psi_j|^2 in the state's own precision: on a
+ * Complex<f32> state they agree with this call to f32 rounding of the products only.)
+ *
+ * Determinism.  No atomics: every block writes its partial sums to the handle's reduction scratch (d_partial) and the host
+ * adds them in block order, as norm_sqr does.  The same call on the same state returns the same bits.
+ *
+ * Reproducibility.  values[t] depends on the state and on term t only: not on which other terms are in the call, on their
+ * order, or on option "expect_group".  A batch equals the single-term calls bit for bit.  (One grid geometry and one
+ * accumulation order per n, precision and class of x mask — zero, bit 0 set, bit 0 clear — whatever the group.)
+ *
+ * Cost.  The terms are sorted by x mask (stably); the terms of one x mask share passes over the vector, at most
+ * "expect_group" terms per pass: one kernel launch and one small copy per pass.  Strings of Z and I (x = 0) are a signed norm
+ * pass.  An empty term is a term of x = 0 like any other and takes a slot of such a pass.
+ *
+ * The state is not changed.  The call is ordered after the work queued on the handle and complete when it returns.  A
+ * relabelled state (option "tile_relabel" = 3) is put back in the caller's order on entry, as by the measurement calls.
+ *
+ * Arguments.  count == 0 returns QIP_OK (null arrays allowed).  With count > 0 each of these is QIP_ERR_INVALID, with a
+ * message: a null array; term_start[0] != 0; a decreasing term_start; a qubit >= n; a qubit repeated inside one term; a code
+ * > 3.  A null handle is QIP_ERR_INVALID: there is no host fall-back.
+ *
+ * State option "expect_group" (set_option of qip_hip.h): the most terms per pass, 1 to 32, anything else is refused with
+ * QIP_ERR_INVALID.  Default 16: the largest kernel capacity (1, 4, 16, 32) whose pass stayed within 1.5x of the single-term
+ * pass in the run recorded in profiles/expect_pauli.md (n = 30, both precisions). */
+int qipx_state_expect_pauli(qip_hip_state* s, const uint64_t* term_start, const uint64_t* qubits,
+                            const uint8_t* paulis, uint64_t count, double* values);
+
+/* Host only, no device needed: the number of passes over the vector the call above makes for these terms on an n-qubit state
+ * when at most `group` terms share a pass (group = 0: the default of "expect_group"; above 32: QIP_ERR_INVALID).  The terms
+ * are checked as above; count == 0 gives 0 passes.  It runs the grouping code the call itself runs. */
+int qipx_expect_pauli_passes(uint32_t n, const uint64_t* term_start, const uint64_t* qubits, const uint8_t* paulis,
+                             uint64_t count, uint32_t group, uint64_t* passes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,9 @@ int make_plan(int dtype, uint32_t n, const FlatOp& f, bool force_generic, Plan* 
 struct qip_hip_state;
 bool sparse_tile_applies(const qip_hip_state* s, const Plan& p, const FlatOp& f);  // qip_launch.hip: the op would run in place through k_sparse_tile
 
+// qipx_state_expect_pauli: the default of option "expect_group" (include/qip_hipx.h says which measurement chose it)
+static constexpr int64_t kExpectGroupDefault = 16;
+
 struct ProfRec {
   int cls;
   hipEvent_t e0, e1;
@@ -167,6 +170,7 @@ struct qip_hip_state {
   void* d_sample = nullptr;
   size_t sample_cap = 0;            // samples the scratch holds
   int64_t sample_slab = 1ll << 22;  // option "sample_slab": samples per slab
+  int64_t expect_group = kExpectGroupDefault;  // option "expect_group": most terms of qipx_state_expect_pauli that share a pass
   // options
   int64_t force_generic = 0;
   int64_t profile = 0;

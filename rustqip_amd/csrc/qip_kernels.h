@@ -2851,6 +2851,122 @@ __global__ __launch_bounds__(kBlock) void k_chunk_norms(const E* __restrict__ st
   if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 
+// ---- expectation values of Pauli strings (qipx_state_expect_pauli, include/qip_hipx.h) -----------------------------------
+// <psi|P|psi> = sum_j conj(psi[j ^ x]) i^nY (-1)^popcount(j & z) psi[j]; the terms of j and j ^ x are conjugates, so a pass
+// walks the pairs (j: bit h of j clear, h = x's highest bit) and adds, per term, +-Re c or +-Im c of c = conj(psi[j ^ x]) psi[j]
+// (the host doubles the sum).  x = 0 (PAIR = false): every amplitude by itself, c = |psi[j]|^2.  All terms of a pass share x,
+// so they share the loads and c; what differs per term is one sign bit per pair and the choice among +-Re, +-Im:
+//   flip   bit g: term g adds -(...)   (nY mod 4 = 1: -Im c, 2: -Re c)
+//   imag   bit g: term g takes Im c    (nY odd)
+//   col    the z masks TRANSPOSED: bit g of col[b] = bit b of the WORK index lies under term g's z mask.  The sign bits of all
+//          terms at work index w are the XOR of col[b] over the set bits b of w: work that grows with the index width, not with
+//          the number of terms, and everything above the lane id is wave-uniform (scalar unit).  A lane's low 8 work-index
+//          bits are its id throughout, so its own share of the sign is the same for every pair it visits: the running sums
+//          are kept with the wave-uniform share of the sign only (the sign word comes from a scalar register) and the lane's
+//          share is applied once, to the finished sum — negation commutes with rounding, the bits are those of signing every
+//          addend.  Per pair and term the vector unit is left with: flip, pick Re / Im, add.
+//   half   packed Complex<f32> (E = f32x4, two amplitudes per element, positions in units of elements): bit g = bit 0 of term
+//          g's z mask, the sign the upper half of an element has on top of the lower one's.
+// Everything is widened to double before the first product.  Slot g's running sum sees the same addends in the same order for
+// every capacity G and whatever the other slots hold: the value of a term does not depend on its company.  A block takes
+// `chunk` contiguous work items (k_chunk_norms' shape: whole spans with U loads per lane 32 KiB apart, then rows of 256) and
+// writes partial[g * gridDim.x + blockIdx.x] for g < count; no atomics.
+constexpr int kExpectMaxGroup = 32;
+struct ExpectDesc {
+  uint64_t x;      // the pass's x mask, in elements
+  uint32_t count;  // slots in use
+  uint32_t flip, imag, half;
+  uint32_t col[64];
+};
+
+template <typename T, int G, bool PAIR, typename E = amp_t<T>>
+__global__ __launch_bounds__(kBlock) void k_expect_pauli(const E* __restrict__ st, uint64_t nwork, uint64_t chunk, Ins ins,
+                                                         ExpectDesc d, double* __restrict__ partial) {
+  constexpr bool PACKED = !SameT<E, amp_t<T>>::v;
+  __shared__ double smem[kBlock / 64];
+  double acc[G];
+#pragma unroll
+  for (int g = 0; g < G; ++g) acc[g] = 0.0;
+  // sign bits of all terms: XOR of col[b] over the set bits of `v`, whose bit 0 is work-index bit `b`
+  auto fold = [&](uint64_t v, uint32_t b) {
+    uint32_t m = 0;
+    for (; v; v >>= 1, ++b)
+      if (v & 1ull) m ^= d.col[b];
+    return m;
+  };
+  uint32_t lane_signs = 0;
+#pragma unroll
+  for (int b = 0; b < 8; ++b) lane_signs ^= ((threadIdx.x >> b) & 1u) ? d.col[b] : 0u;
+  auto add = [&](uint32_t signs, double cr, double ci) {
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      const double v = (PAIR && ((d.imag >> g) & 1u)) ? ci : cr;
+      const uint64_t sign = (uint64_t)((signs >> g) & 1u) << 63;
+      acc[g] += __longlong_as_double(__double_as_longlong(v) ^ (long long)sign);
+    }
+  };
+  // a = the element at j, b = the element at j ^ x; `signs` = the wave-uniform share of the terms' sign bits at j (its lower
+  // half, when packed)
+  auto take = [&](uint32_t signs, E a, E b) {
+    if constexpr (PACKED) {
+      const double ax = a.x, ay = a.y, az = a.z, aw = a.w;
+      if constexpr (PAIR) {
+        const double bx = b.x, by = b.y, bz = b.z, bw = b.w;
+        add(signs, bx * ax + by * ay, bx * ay - by * ax);
+        add(signs ^ d.half, bz * az + bw * aw, bz * aw - bw * az);
+      } else {
+        add(signs, ax * ax + ay * ay, 0.0);
+        add(signs ^ d.half, az * az + aw * aw, 0.0);
+      }
+    } else {
+      const double ax = a.x, ay = a.y;
+      if constexpr (PAIR) {
+        const double bx = b.x, by = b.y;
+        add(signs, bx * ax + by * ay, bx * ay - by * ax);
+      } else {
+        add(signs, ax * ax + ay * ay, 0.0);
+      }
+    }
+  };
+  auto index_of = [&](uint64_t w) { return PAIR ? insert_bits<1>(w, ins) : w; };
+  constexpr int LOGU = PAIR ? 1 : 2, U = 1 << LOGU;  // four 16-byte loads in flight per lane either way
+  constexpr uint64_t kSpan = (uint64_t)U << kStrideShift;
+  const uint64_t lo = (uint64_t)blockIdx.x * chunk;
+  const uint64_t hi = lo + chunk < nwork ? lo + chunk : nwork;
+  uint64_t i = lo;  // (a multiple of 256 throughout: the lane id is the work index's low 8 bits)
+  for (; i + kSpan <= hi; i += kSpan) {
+    const uint32_t span_signs = d.flip ^ fold(i >> (kStrideShift + LOGU), kStrideShift + LOGU);
+#pragma unroll 1
+    for (uint32_t qrow = 0; qrow < (1u << (kStrideShift - 8)); ++qrow) {
+      const uint64_t w0 = i + (uint64_t)qrow * kBlock + threadIdx.x;
+      const uint32_t row_signs = span_signs ^ fold(qrow, 8);
+      E a[U], b[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const uint64_t j = index_of(w0 + ((uint64_t)u << kStrideShift));
+        a[u] = __builtin_nontemporal_load(st + j);
+        if constexpr (PAIR) b[u] = __builtin_nontemporal_load(st + (j ^ d.x));
+        else b[u] = a[u];
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) take(row_signs ^ fold(u, kStrideShift), a[u], b[u]);
+    }
+  }
+  for (; i < hi; i += kBlock) {
+    const uint64_t w = i + threadIdx.x;
+    if (w < hi) {
+      const uint64_t j = index_of(w);
+      const E a = st[j];
+      take(d.flip ^ fold(i >> 8, 8), a, PAIR ? st[j ^ d.x] : a);
+    }
+  }
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const double t = block_reduce_sum(((lane_signs >> g) & 1u) ? -acc[g] : acc[g], smem);
+    if (threadIdx.x == 0 && (uint32_t)g < d.count) partial[(uint64_t)g * gridDim.x + blockIdx.x] = t;
+  }
+}
+
 // Two states compared amplitude by amplitude over the whole vector (qip_hip_state_max_abs_diff: how far a state is from a
 // reference copy): partial[2 b] = max |a_i - b_i| over block b's share, partial[2 b + 1] = number of amplitudes whose
 // components are not IEEE-equal (NaNs count as different).  Grid-stride, one coalesced pass over both vectors.

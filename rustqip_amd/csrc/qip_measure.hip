@@ -559,6 +559,192 @@ extern "C" int qipx_state_soft_measure_many(qip_hip_state* s, const uint64_t* in
                              : soft_measure_many_t<float>(s, md, rand_u01, count, measured);
 } QIP_CATCH_ALL
 
+// ---- expectation values of Pauli strings (include/qip_hipx.h) -----------------------------------------------------------
+//   reduce  every term to (x mask, z mask, n_Y mod 4) over amplitude-index bits (expect_reduce)
+//   plan    the terms sorted by x mask, stably, each run of one x cut into passes of at most `group` terms (expect_plan: also
+//           all that qipx_expect_pauli_passes runs)
+//   pass    one k_expect_pauli launch + one copy of its per-block partial sums; as many passes share a synchronise as their
+//           partial sums fit the scratch; the host adds a term's partial sums in block order and doubles the pair passes
+// The geometry of a pass (expect_geom) depends on n, the precision and the class of the x mask only (zero / bit 0 set / bit 0
+// clear), never on the group: together with the kernel's per-slot sums that makes a value a function of the state and its term.
+namespace {
+struct PauliTerm {
+  uint64_t x, z;
+  uint32_t ny;  // n_Y mod 4
+};
+struct ExpectPass {
+  uint32_t first, count;  // the terms order[first .. first + count), all of one x mask
+};
+struct ExpectGeom {
+  bool pair, packed;
+  uint64_t nwork, chunk;
+  uint32_t nblocks, shift, hbit;  // shift: 1 = positions in 16-byte elements of two amplitudes; hbit: x's highest bit, in elements
+};
+}  // namespace
+
+static int expect_reduce(uint32_t n, const uint64_t* term_start, const uint64_t* qubits, const uint8_t* paulis, uint64_t count,
+                         std::vector<PauliTerm>* terms) {
+  if (n > 63) return fail(QIP_ERR_INVALID, "expect_pauli: %u qubits", n);
+  if (!term_start || !qubits || !paulis) return fail(QIP_ERR_INVALID, "expect_pauli: null term array");
+  if (term_start[0] != 0) return fail(QIP_ERR_INVALID, "expect_pauli: term_start[0] is not 0");
+  terms->resize(count);
+  for (uint64_t t = 0; t < count; ++t) {
+    if (term_start[t + 1] < term_start[t]) return fail(QIP_ERR_INVALID, "expect_pauli: term_start decreases at term %llu", (unsigned long long)t);
+    PauliTerm pt{0, 0, 0};
+    uint64_t seen = 0;
+    for (uint64_t i = term_start[t]; i < term_start[t + 1]; ++i) {
+      if (qubits[i] >= n) return fail(QIP_ERR_INVALID, "expect_pauli: qubit %llu of term %llu out of range", (unsigned long long)qubits[i], (unsigned long long)t);
+      if (paulis[i] > 3) return fail(QIP_ERR_INVALID, "expect_pauli: Pauli code %u in term %llu", (unsigned)paulis[i], (unsigned long long)t);
+      const uint64_t bit = 1ull << (n - 1 - qubits[i]);
+      if (seen & bit) return fail(QIP_ERR_INVALID, "expect_pauli: qubit %llu repeated in term %llu", (unsigned long long)qubits[i], (unsigned long long)t);
+      seen |= bit;
+      if (paulis[i] == 1 || paulis[i] == 2) pt.x |= bit;
+      if (paulis[i] == 2 || paulis[i] == 3) pt.z |= bit;
+      if (paulis[i] == 2) pt.ny = (pt.ny + 1) & 3u;
+    }
+    (*terms)[t] = pt;
+  }
+  return QIP_OK;
+}
+
+static void expect_plan(const std::vector<PauliTerm>& terms, uint32_t group, std::vector<uint32_t>* order, std::vector<ExpectPass>* passes) {
+  order->resize(terms.size());
+  for (size_t t = 0; t < terms.size(); ++t) (*order)[t] = (uint32_t)t;
+  std::stable_sort(order->begin(), order->end(), [&](uint32_t a, uint32_t b) { return terms[a].x < terms[b].x; });
+  passes->clear();
+  for (size_t at = 0; at < order->size();) {
+    size_t end = at;
+    while (end < order->size() && terms[(*order)[end]].x == terms[(*order)[at]].x) ++end;
+    for (; at < end; at += std::min<size_t>(group, end - at))
+      passes->push_back(ExpectPass{(uint32_t)at, (uint32_t)std::min<size_t>(group, end - at)});
+  }
+}
+
+extern "C" int qipx_expect_pauli_passes(uint32_t n, const uint64_t* term_start, const uint64_t* qubits, const uint8_t* paulis,
+                                        uint64_t count, uint32_t group, uint64_t* passes) try {
+  if (!passes) return fail(QIP_ERR_INVALID, "null output");
+  if (group > (uint32_t)kExpectMaxGroup) return fail(QIP_ERR_INVALID, "expect_group is 1 to %d", kExpectMaxGroup);
+  *passes = 0;
+  if (count == 0) return QIP_OK;
+  if (count > 0xffffffffull) return fail(QIP_ERR_UNSUPPORTED, "expect_pauli: more than 2^32 - 1 terms");
+  std::vector<PauliTerm> terms;
+  QCHK(expect_reduce(n, term_start, qubits, paulis, count, &terms));
+  std::vector<uint32_t> order;
+  std::vector<ExpectPass> plan;
+  expect_plan(terms, group ? group : (uint32_t)kExpectGroupDefault, &order, &plan);
+  *passes = plan.size();
+  return QIP_OK;
+} QIP_CATCH_ALL
+
+static uint32_t top_bit(uint64_t v) {
+  uint32_t b = 0;
+  while (v >>= 1) ++b;
+  return b;
+}
+
+template <typename T>
+static ExpectGeom expect_geom(const qip_hip_state* s, uint64_t x) {
+  ExpectGeom g;
+  g.pair = x != 0;
+  // Complex<f32>: 16-byte elements of two amplitudes unless the pair differs in index bit 0 (its halves would cross elements)
+  g.packed = std::is_same<T, float>::value && s->packed_f32 && s->n >= 2 && (x & 1ull) == 0;
+  g.shift = g.packed ? 1u : 0u;
+  g.hbit = g.pair ? top_bit(x) - g.shift : 0u;
+  g.nwork = (s->namps >> g.shift) >> (g.pair ? 1 : 0);
+  const uint64_t span = (uint64_t)(g.pair ? 2 : 4) << kStrideShift;  // one round of k_expect_pauli's main loop
+  g.chunk = std::min<uint64_t>(std::max<uint64_t>(g.nwork / 4096, span), g.nwork);
+  g.nblocks = (uint32_t)((g.nwork + g.chunk - 1) / g.chunk);
+  return g;
+}
+
+template <typename T, int G>
+static void expect_launch_g(qip_hip_state* s, const ExpectGeom& g, const Ins& ins, const ExpectDesc& d, double* partial) {
+  const dim3 grid(g.nblocks), block(kBlock);
+  if (g.packed && g.pair)
+    hipLaunchKernelGGL((k_expect_pauli<float, G, true, f32x4>), grid, block, 0, s->stream, (const f32x4*)s->cur, g.nwork, g.chunk, ins, d, partial);
+  else if (g.packed)
+    hipLaunchKernelGGL((k_expect_pauli<float, G, false, f32x4>), grid, block, 0, s->stream, (const f32x4*)s->cur, g.nwork, g.chunk, ins, d, partial);
+  else if (g.pair)
+    hipLaunchKernelGGL((k_expect_pauli<T, G, true>), grid, block, 0, s->stream, (const amp_t<T>*)s->cur, g.nwork, g.chunk, ins, d, partial);
+  else
+    hipLaunchKernelGGL((k_expect_pauli<T, G, false>), grid, block, 0, s->stream, (const amp_t<T>*)s->cur, g.nwork, g.chunk, ins, d, partial);
+}
+
+// one pass: the terms `ids` (all of x mask `x`), partial sums to partial[slot * nblocks + block]
+template <typename T>
+static int expect_launch(qip_hip_state* s, const ExpectGeom& g, uint64_t x, const std::vector<PauliTerm>& terms, const uint32_t* ids,
+                         uint32_t count, double* partial) {
+  ExpectDesc d;
+  memset(&d, 0, sizeof d);
+  d.x = x >> g.shift;
+  d.count = count;
+  for (uint32_t slot = 0; slot < count; ++slot) {
+    const PauliTerm& t = terms[ids[slot]];
+    if (t.ny == 1 || t.ny == 2) d.flip |= 1u << slot;
+    if (t.ny & 1u) d.imag |= 1u << slot;
+    if (g.packed && (t.z & 1ull)) d.half |= 1u << slot;
+    for (uint32_t b = 0; b + g.shift + (g.pair ? 1 : 0) < s->n; ++b) {
+      const uint32_t pos = (g.pair && b >= g.hbit ? b + 1 : b) + g.shift;  // the amplitude-index bit behind work-index bit b
+      if ((t.z >> pos) & 1ull) d.col[b] |= 1u << slot;
+    }
+  }
+  const Ins ins = g.pair ? make_ins({g.hbit}, 0) : make_ins({}, 0);
+  if (count <= 1) expect_launch_g<T, 1>(s, g, ins, d, partial);
+  else if (count <= 4) expect_launch_g<T, 4>(s, g, ins, d, partial);
+  else if (count <= 16) expect_launch_g<T, 16>(s, g, ins, d, partial);
+  else expect_launch_g<T, kExpectMaxGroup>(s, g, ins, d, partial);
+  HIPCHK(hipGetLastError());
+  return QIP_OK;
+}
+
+template <typename T>
+static int expect_pauli_t(qip_hip_state* s, const std::vector<PauliTerm>& terms, double* values) {
+  std::vector<uint32_t> order;
+  std::vector<ExpectPass> plan;
+  expect_plan(terms, (uint32_t)s->expect_group, &order, &plan);
+  std::vector<ExpectGeom> geom(plan.size());
+  size_t total = 0;
+  for (size_t p = 0; p < plan.size(); ++p) {
+    geom[p] = expect_geom<T>(s, terms[order[plan[p].first]].x);
+    total += (size_t)plan[p].count * geom[p].nblocks;
+  }
+  // the passes that share a synchronise: as many as keep their partial sums within 2^20 doubles (one pass needs <= 32 * 4096)
+  const size_t cap = std::min<size_t>(total, (size_t)1 << 20);
+  QCHK(ensure_partial(s, cap));
+  std::vector<double> part(cap);
+  for (size_t p = 0; p < plan.size();) {
+    size_t used = 0, q = p;
+    for (; q < plan.size(); ++q) {
+      const size_t need = (size_t)plan[q].count * geom[q].nblocks;
+      if (used + need > cap) break;
+      QCHK(expect_launch<T>(s, geom[q], terms[order[plan[q].first]].x, terms, order.data() + plan[q].first, plan[q].count, s->d_partial + used));
+      HIPCHK(hipMemcpyAsync(part.data() + used, s->d_partial + used, need * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+      used += need;
+    }
+    HIPCHK(hipStreamSynchronize(s->stream));
+    for (size_t at = 0; p < q; ++p) {
+      const uint32_t nb = geom[p].nblocks;
+      for (uint32_t slot = 0; slot < plan[p].count; ++slot, at += nb) {
+        double t = 0;
+        for (uint32_t b = 0; b < nb; ++b) t += part[at + b];
+        values[order[plan[p].first + slot]] = geom[p].pair ? 2.0 * t : t;
+      }
+    }
+  }
+  return QIP_OK;
+}
+
+extern "C" int qipx_state_expect_pauli(qip_hip_state* s, const uint64_t* term_start, const uint64_t* qubits, const uint8_t* paulis,
+                                       uint64_t count, double* values) try {
+  STATE_ENTER(s);
+  if (count == 0) return QIP_OK;
+  if (!values) return fail(QIP_ERR_INVALID, "expect_pauli: null result array");
+  if (count > 0xffffffffull) return fail(QIP_ERR_UNSUPPORTED, "expect_pauli: more than 2^32 - 1 terms");
+  std::vector<PauliTerm> terms;
+  QCHK(expect_reduce(s->n, term_start, qubits, paulis, count, &terms));
+  return s->dtype == QIP_C64 ? expect_pauli_t<double>(s, terms, values) : expect_pauli_t<float>(s, terms, values);
+} QIP_CATCH_ALL
+
 extern "C" int qip_hip_state_measure(qip_hip_state* s, const uint64_t* indices, uint32_t k,
                                      int64_t forced, double rand_u01, uint64_t* measured, double* prob) try {
   STATE_ENTER(s);

@@ -372,6 +372,25 @@ template <typename P> class HipState {
     check(qipx_state_soft_measure_many(h_, idx.data(), (uint32_t)idx.size(), rand_u01.data(), rand_u01.size(), out.data()));
     return out;
   }
+  /// <psi| P |psi> of Pauli strings (qip_hipx.h, beyond the reference's interface): a term is a list of (qubit, code), code
+  /// 0 = I, 1 = X, 2 = Y, 3 = Z.  The raw quadratic form, in double for both precisions; the state is not changed.
+  std::vector<double> expect_pauli(const std::vector<std::vector<std::pair<size_t, int>>>& terms) const {
+    std::vector<uint64_t> start(1, 0), qubits;
+    std::vector<uint8_t> paulis;
+    for (const auto& term : terms) {
+      for (const auto& f : term) {
+        if (f.second < 0 || f.second > 255) throw std::invalid_argument("expect_pauli: Pauli code out of range");
+        qubits.push_back(f.first);
+        paulis.push_back(uint8_t(f.second));
+      }
+      start.push_back(qubits.size());
+    }
+    qubits.push_back(0);  // (never a null data() for a list of empty terms)
+    paulis.push_back(0);
+    std::vector<double> out(terms.size());
+    check(qipx_state_expect_pauli(h_, start.data(), qubits.data(), paulis.data(), terms.size(), out.data()));
+    return out;
+  }
   std::vector<double> measure_probs(const std::vector<size_t>& indices) const {
     std::vector<uint64_t> idx(indices.begin(), indices.end());
     std::vector<double> out(size_t(1) << idx.size());

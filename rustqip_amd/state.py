@@ -181,6 +181,41 @@ def ext_abi_version() -> int:
     return int(_ffi.lib.qipx_abi_version())
 
 
+_PAULI_CODES = {"I": 0, "X": 1, "Y": 2, "Z": 3}
+
+
+def _pauli_terms(n: int, terms):
+    """(term_start, qubits, paulis, count) of include/qip_hipx.h for a list of terms: a term is a mapping {qubit: "X" | "Y" |
+    "Z" | "I"} or a string of length n over IXYZ whose character q acts on qubit q"""
+    start, qubits, paulis = [0], [], []
+    for term in terms:
+        if isinstance(term, str):
+            if len(term) != n:
+                raise CircuitError(f"a Pauli string on {n} qubits has {n} characters, not {len(term)}")
+            factors = enumerate(term)
+        else:
+            factors = term.items()
+        for q, p in factors:
+            code = _PAULI_CODES.get(p.upper() if isinstance(p, str) else p)
+            if code is None:
+                raise CircuitError(f"not a Pauli factor: {p!r} (use I, X, Y or Z)")
+            if isinstance(term, str) and code == 0:
+                continue
+            qubits.append(int(q))
+            paulis.append(code)
+        start.append(len(qubits))
+    return _u64_array(start), _u64_array(qubits), (C.c_uint8 * len(paulis))(*paulis), len(start) - 1
+
+
+def expect_pauli_passes(n: int, terms, group: int = 0) -> int:
+    """Passes over the vector HipState.expect_pauli makes for `terms` on an n-qubit state when at most `group` terms share a
+    pass (0: the default of option "expect_group").  Host only: no device is needed."""
+    start, qubits, paulis, count = _pauli_terms(n, terms)
+    out = C.c_uint64()
+    _check(_ffi.lib.qipx_expect_pauli_passes(int(n), start, qubits, paulis, count, int(group), C.byref(out)))
+    return int(out.value)
+
+
 def _u64_array(values: Sequence[int]):
     arr = (C.c_uint64 * len(values))(*[int(v) for v in values])
     return arr
@@ -372,6 +407,24 @@ class HipState:
         """`shots` outcomes of measuring `indices`, the state left as it is: soft_measure_many over the uniform draws of
         np.random.Generator(np.random.PCG64(seed))"""
         return self.soft_measure_many(indices, np.random.Generator(np.random.PCG64(seed)).random(int(shots)))
+
+    def expect_pauli(self, terms) -> np.ndarray:
+        """float64[len(terms)]: <psi| P |psi> of every Pauli string in `terms` (include/qip_hipx.h): a term is a mapping
+        {qubit: "X" | "Y" | "Z" | "I"} or a string of length n over IXYZ, character q acting on qubit q.  The raw quadratic
+        form (not divided by the norm), in double for both precisions; terms with the same X/Y qubits share passes over the
+        vector, and a value does not depend on the other terms of the call.  The state is not changed."""
+        start, qubits, paulis, count = _pauli_terms(self.n, terms)
+        out = np.empty(count, dtype=np.float64)
+        _check(_ffi.lib.qipx_state_expect_pauli(self._h, start, qubits, paulis, count, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def expectation(self, terms, coeffs) -> float:
+        """<psi| H |psi> of H = sum_t coeffs[t] * terms[t] with real coefficients: the dot product with expect_pauli(terms)"""
+        terms = list(terms)
+        c = np.asarray(coeffs, dtype=np.float64).reshape(-1)
+        if len(c) != len(terms):
+            raise CircuitError(f"{len(terms)} terms but {len(c)} coefficients")
+        return float(np.dot(c, self.expect_pauli(terms)))
 
     def measure(self, indices: Sequence[int], measured: Optional[int] = None,
                 rand_u01: float = 0.0) -> Tuple[int, float]:
