@@ -153,6 +153,26 @@ impl<P: HipPrecision> HipState<P> {
         })?;
         Ok(out)
     }
+    /// psi <- exp(-i * angles[t] * P_t) psi for every term, in the order given (`include/qip_hipx.h`): terms as for
+    /// `expect_pauli`.  One in-place pass per run of consecutive terms with the same X/Y qubits; queued on the stream, returns
+    /// without waiting.
+    pub fn apply_pauli_rotations(&mut self, terms: &[Vec<(u64, u8)>], angles: &[f64]) -> Result<(), HipError> {
+        assert_eq!(terms.len(), angles.len(), "one angle per term");
+        let mut start = vec![0u64];
+        let (mut qubits, mut paulis) = (Vec::new(), Vec::new());
+        for term in terms {
+            for &(q, p) in term {
+                qubits.push(q);
+                paulis.push(p);
+            }
+            start.push(qubits.len() as u64);
+        }
+        qubits.push(0);
+        paulis.push(0);
+        check(unsafe {
+            sys_ext::qipx_state_apply_pauli_rotations(self.h, start.as_ptr(), qubits.as_ptr(), paulis.as_ptr(), angles.as_ptr(), terms.len() as u64)
+        })
+    }
     pub fn raw(&mut self) -> *mut sys::qip_hip_state {
         self.h
     }

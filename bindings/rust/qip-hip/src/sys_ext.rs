@@ -37,4 +37,25 @@ extern "C" {
         group: u32,
         passes: *mut u64,
     ) -> c_int;
+    /// psi <- exp(-i * angles[t] * P_t) psi for `t < count`, in the order given; the terms as for `qipx_state_expect_pauli`.
+    /// Queued on the handle's stream, returns without waiting.
+    pub fn qipx_state_apply_pauli_rotations(
+        s: *mut qip_hip_state,
+        term_start: *const u64,
+        qubits: *const u64,
+        paulis: *const u8,
+        angles: *const c_double,
+        count: u64,
+    ) -> c_int;
+    /// Host only: the passes over the vector the call above makes when at most `group` consecutive terms of one X/Y mask
+    /// share one (0 = the default).
+    pub fn qipx_pauli_rotation_passes(
+        n: u32,
+        term_start: *const u64,
+        qubits: *const u64,
+        paulis: *const u8,
+        count: u64,
+        group: u32,
+        passes: *mut u64,
+    ) -> c_int;
 }

@@ -85,6 +85,53 @@ int qipx_state_expect_pauli(qip_hip_state* s, const uint64_t* term_start, const 
 int qipx_expect_pauli_passes(uint32_t n, const uint64_t* term_start, const uint64_t* qubits, const uint8_t* paulis,
                              uint64_t count, uint32_t group, uint64_t* passes);
 
+/* Pauli-string rotations in place.  (Added without a change of QIPX_ABI_VERSION: purely additive again.)
+ *
+ * For t = 0 .. count-1, IN THE ORDER GIVEN, psi <- exp(-i * angles[t] * P_t) psi.  The terms are given exactly as for
+ * qipx_state_expect_pauli above (the same arrays, the same codes, qubit q = index bit n-1-q) and are checked by the same code
+ * with the same messages.  Nothing is reordered: the terms do not commute in general.
+ *
+ * The rotation.  exp(-i theta P) = cos theta * I - i sin theta * P, and with x, z, n_Y as above
+ *   (P psi)[j] = i^n_Y * (-1)^popcount((j ^ x) & z) * psi[j ^ x],
+ * so every amplitude mixes with one partner only: one in-place pass that reads and writes each amplitude once, whatever the
+ * weight of the string.  An empty term, and a term of I factors only, is the global phase e^{-i theta}: a term of x = 0 like
+ * any other (a Z string multiplies psi[j] by e^{-+ i theta}).
+ *
+ * Arithmetic.  c = cos theta and s = sin theta are evaluated in double on the host and rounded once to the state's precision.
+ * The factor -i * i^n_Y * (+-1) is a swap or negation of components, which is exact.  Every new component is
+ *   fl(fl(c * u) + fl(s * v))
+ * in the state's precision, u the old component and v the signed component of the partner (of the amplitude itself when
+ * x = 0); no fused multiply-add, and zero amplitudes get no special case.  Per component the error of one rotation is at most
+ * 4u(|c||u| + |s||v|) with u the unit roundoff (2^-53, 2^-24): rounding of c and s, two products, one sum.
+ *
+ * Reproducibility.  A batch leaves the bits that the single-term calls leave when made one after the other, under any value
+ * of option "rotate_group": a slot of a pass does the same operations on the same values whatever its company.
+ *
+ * Cost.  A pass takes a maximal run of CONSECUTIVE terms of equal x mask, cut at "rotate_group" terms: it loads each pair
+ * (j, j ^ x) once, applies the run's rotations to it one after the other in registers, in term order, and stores it: one kernel
+ * launch per pass, no synchronisation, no atomics.  The eight strings of a Jordan-Wigner double excitation share one x mask; a
+ * whole QAOA cost layer is x = 0.  Terms of one x mask that are separated by a term of another do not share a pass.
+ *
+ * Calling contract.  The call is queued on the handle's stream behind earlier work and returns without waiting, like
+ * qip_hip_state_apply_op.  A relabelled state (option "tile_relabel" = 3) is put back in the caller's order on entry.
+ * count == 0 returns QIP_OK (null arrays allowed).  With count > 0 each of these is QIP_ERR_INVALID with a message, and leaves
+ * the state untouched (everything is checked before the first launch): a null array; a non-finite angle (the message names the
+ * term); any term error of qipx_state_expect_pauli.  A null handle is QIP_ERR_INVALID: there is no host fall-back.  More than
+ * 2^32 - 1 terms is QIP_ERR_UNSUPPORTED.
+ *
+ * State option "rotate_group": the most terms per pass, 1 to 32, anything else is refused with QIP_ERR_INVALID.
+ * Default 16: the largest of 1, 4, 16, 32 terms whose pass stayed within 1.5x of the single-term pass in the run recorded in
+ * profiles/pauli_rotation.md (tools/bench_rotate.py, n = 30, both precisions: 16 terms 1.25x / 1.34x, 32 terms 2.27x / 2.47x; a
+ * pass of more than a few terms is bound by vector issue, about 0.4 ms per term and pass in Complex<f64>, not by memory). */
+int qipx_state_apply_pauli_rotations(qip_hip_state* s, const uint64_t* term_start, const uint64_t* qubits,
+                                     const uint8_t* paulis, const double* angles, uint64_t count);
+
+/* Host only, no device needed: the number of passes over the vector the call above makes for these terms on an n-qubit state
+ * when at most `group` terms share a pass (group = 0: the default of "rotate_group"; above 32: QIP_ERR_INVALID).  The terms
+ * are checked as above; count == 0 gives 0 passes.  It runs the grouping code the call itself runs. */
+int qipx_pauli_rotation_passes(uint32_t n, const uint64_t* term_start, const uint64_t* qubits, const uint8_t* paulis,
+                               uint64_t count, uint32_t group, uint64_t* passes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,6 +166,8 @@ EXT_SIGNATURES = {
     "qipx_state_soft_measure_many": (_int, [_statep, _u64p, _u32, _dblp, _u64, _u64p]),
     "qipx_state_expect_pauli": (_int, [_statep, _u64p, _u64p, C.POINTER(C.c_uint8), _u64, _dblp]),
     "qipx_expect_pauli_passes": (_int, [_u32, _u64p, _u64p, C.POINTER(C.c_uint8), _u64, _u32, _u64p]),
+    "qipx_state_apply_pauli_rotations": (_int, [_statep, _u64p, _u64p, C.POINTER(C.c_uint8), _dblp, _u64]),
+    "qipx_pauli_rotation_passes": (_int, [_u32, _u64p, _u64p, C.POINTER(C.c_uint8), _u64, _u32, _u64p]),
 }
 
 

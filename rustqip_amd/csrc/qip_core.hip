@@ -576,6 +576,10 @@ extern "C" int qip_hip_state_set_option(qip_hip_state* s, const char* key, int64
     if (value < 1 || value > kExpectMaxGroup) return fail(QIP_ERR_INVALID, "expect_group is 1 to %d", kExpectMaxGroup);
     s->expect_group = value;
   }
+  else if (!strcmp(key, "rotate_group")) {
+    if (value < 1 || value > kRotateMaxGroup) return fail(QIP_ERR_INVALID, "rotate_group is 1 to %d", kRotateMaxGroup);
+    s->rotate_group = value;
+  }
 #ifdef QIP_HIP_TUNING
   else if (!strcmp(key, "lowbit_shuffle")) s->lowbit_shuffle = value;
   else if (!strcmp(key, "packed_f32")) s->packed_f32 = value;

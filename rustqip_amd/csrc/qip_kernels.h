@@ -39,6 +39,7 @@ template <> struct V2<float> { using type = float __attribute__((ext_vector_type
 template <typename T> using amp_t = typename V2<T>::type;
 template <typename A, typename B> struct SameT { static constexpr bool v = false; };  // (std::is_same: no system headers under hiprtc)
 template <typename A> struct SameT<A, A> { static constexpr bool v = true; };
+template <int V> struct IntC { static constexpr int v = V; };  // an int as a type: a lambda's compile-time argument
 
 // ---- index arithmetic ------------------------------------------------------
 
@@ -2872,6 +2873,21 @@ __global__ __launch_bounds__(kBlock) void k_chunk_norms(const E* __restrict__ st
 // `chunk` contiguous work items (k_chunk_norms' shape: whole spans with U loads per lane 32 KiB apart, then rows of 256) and
 // writes partial[g * gridDim.x + blockIdx.x] for g < count; no atomics.
 constexpr int kExpectMaxGroup = 32;
+// The sign words of a pass over transposed z masks (k_expect_pauli, k_pauli_rotate): the XOR of col[b] over the set bits of `v`,
+// whose bit 0 is work-index bit `b` ...
+__device__ __forceinline__ uint32_t pauli_fold(const uint32_t (&col)[64], uint64_t v, uint32_t b) {
+  uint32_t m = 0;
+  for (; v; v >>= 1, ++b)
+    if (v & 1ull) m ^= col[b];
+  return m;
+}
+// ... and a lane's own share of them: its id is the low 8 bits of every work index it visits
+__device__ __forceinline__ uint32_t pauli_lane_signs(const uint32_t (&col)[64]) {
+  uint32_t m = 0;
+#pragma unroll
+  for (int b = 0; b < 8; ++b) m ^= ((threadIdx.x >> b) & 1u) ? col[b] : 0u;
+  return m;
+}
 struct ExpectDesc {
   uint64_t x;      // the pass's x mask, in elements
   uint32_t count;  // slots in use
@@ -2887,16 +2903,8 @@ __global__ __launch_bounds__(kBlock) void k_expect_pauli(const E* __restrict__ s
   double acc[G];
 #pragma unroll
   for (int g = 0; g < G; ++g) acc[g] = 0.0;
-  // sign bits of all terms: XOR of col[b] over the set bits of `v`, whose bit 0 is work-index bit `b`
-  auto fold = [&](uint64_t v, uint32_t b) {
-    uint32_t m = 0;
-    for (; v; v >>= 1, ++b)
-      if (v & 1ull) m ^= d.col[b];
-    return m;
-  };
-  uint32_t lane_signs = 0;
-#pragma unroll
-  for (int b = 0; b < 8; ++b) lane_signs ^= ((threadIdx.x >> b) & 1u) ? d.col[b] : 0u;
+  auto fold = [&](uint64_t v, uint32_t b) { return pauli_fold(d.col, v, b); };  // sign bits of all terms
+  const uint32_t lane_signs = pauli_lane_signs(d.col);
   auto add = [&](uint32_t signs, double cr, double ci) {
 #pragma unroll
     for (int g = 0; g < G; ++g) {
@@ -2964,6 +2972,156 @@ __global__ __launch_bounds__(kBlock) void k_expect_pauli(const E* __restrict__ s
   for (int g = 0; g < G; ++g) {
     const double t = block_reduce_sum(((lane_signs >> g) & 1u) ? -acc[g] : acc[g], smem);
     if (threadIdx.x == 0 && (uint32_t)g < d.count) partial[(uint64_t)g * gridDim.x + blockIdx.x] = t;
+  }
+}
+
+// ---- Pauli-string rotations exp(-i theta P) in place (qipx_state_apply_pauli_rotations, include/qip_hipx.h) -----------------
+// exp(-i theta P) = cos theta - i sin theta P mixes psi[j] with psi[j ^ x] only, so a pass walks the pairs of k_expect_pauli in
+// k_expect_pauli's geometry (PAIR, PACKED, `ins`, `chunk`, spans and rows as there), keeps a pair in registers, sends it through
+// the pass's slots one after the other — consecutive terms of one x mask, in term order — and stores it: every amplitude is read
+// once and written once, by the one lane that owns its pair; no LDS, no atomics, no synchronisation.  Slot g, with c = cos
+// theta_g, s = sin theta_g rounded once to T on the host, p = (n_Y + 3) mod 4 (-i i^n_Y = i^p) and sigma_m = (-1)^popcount(m & z):
+//   psi'[j] = c psi[j] + s i^p sigma_{j^x} psi[j ^ x],     psi'[j ^ x] = c psi[j ^ x] + s i^p sigma_j psi[j],
+// i^p and sigma a swap and sign flips of components (exact), every new component fl(fl(c u) + fl(s v)), never fused (the file
+// is compiled with contraction off).  sigma_j comes from the transposed z masks as in k_expect_pauli (the lane's share is XORed in
+// per pair here: the pair is written, not summed); sigma_{j^x} = sigma_j (-1)^n_Y.
+//   swap   bit g: p odd — the partner's components change places
+//   hi     bit g: p >= 2
+//   odd    bit g: n_Y odd
+//   half   packed Complex<f32>: bit 0 of slot g's z mask, as in ExpectDesc
+// Slots >= count are skipped, not multiplied through with c = 1, s = 0 (that would turn -0 into +0 and 0 * inf into NaN).  A slot
+// does the same operations on the same values whatever the capacity G and whatever its company: any grouping leaves the same bits.
+constexpr int kRotateMaxGroup = 32;
+template <typename T> struct RotateDesc {
+  uint64_t x;      // the pass's x mask, in elements
+  uint32_t count;  // slots in use
+  uint32_t swap, hi, odd, half;
+  uint32_t col[64];
+  T c[kRotateMaxGroup], s[kRotateMaxGroup];
+};
+__device__ __forceinline__ float flip_sign(float v, uint32_t bit) { return __uint_as_float(__float_as_uint(v) ^ (bit << 31)); }
+__device__ __forceinline__ double flip_sign(double v, uint32_t bit) {
+  return __longlong_as_double(__double_as_longlong(v) ^ (long long)((uint64_t)bit << 63));
+}
+
+// one amplitude's components through one slot: (ur, ui) <- c (ur, ui) + s i^P (vr, vi), `s` already signed with sigma
+template <int P, typename T> __device__ __forceinline__ void pauli_mix(T c, T s, T& ur, T& ui, T vr, T vi) {
+  T xr, xi;  // i^P (vr, vi): 0: (vr, vi)  1: (-vi, vr)  2: (-vr, -vi)  3: (vi, -vr); s * (-v) = (-s) * v = -(s * v), bit for bit
+  if constexpr (P == 0) xr = s * vr, xi = s * vi;
+  else if constexpr (P == 1) xr = -(s * vi), xi = s * vr;
+  else if constexpr (P == 2) xr = -(s * vr), xi = -(s * vi);
+  else xr = s * vi, xi = -(s * vr);
+  ur = c * ur + xr;
+  ui = c * ui + xi;
+}
+
+// K = the amplitudes a lane holds per side: U elements, twice that when packed.  Slot g on all of them; sj[k] = the sign word of
+// amplitude k (bit g: sigma_j negative).  The sign goes onto s (one XOR per amplitude and side), i^P is a wave-uniform case.
+template <int P, bool PAIR, int K, typename T>
+__device__ __forceinline__ void pauli_slot(T c, T s, uint32_t g, uint32_t odd, const uint32_t (&sj)[K], T (&ar)[K], T (&ai)[K],
+                                           T (&br)[K], T (&bi)[K]) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const uint32_t bit = (sj[k] >> g) & 1u;
+    if constexpr (PAIR) {
+      const T ur = ar[k], ui = ai[k];
+      pauli_mix<P>(c, flip_sign(s, bit ^ odd), ar[k], ai[k], br[k], bi[k]);  // sigma_{j^x} = sigma_j (-1)^n_Y
+      pauli_mix<P>(c, flip_sign(s, bit), br[k], bi[k], ur, ui);
+    } else {
+      pauli_mix<P>(c, flip_sign(s, bit), ar[k], ai[k], ar[k], ai[k]);
+    }
+  }
+}
+
+template <typename T, int G, bool PAIR, typename E = amp_t<T>>
+__global__ __launch_bounds__(kBlock) void k_pauli_rotate(E* __restrict__ st, uint64_t nwork, uint64_t chunk, Ins ins, RotateDesc<T> d) {
+  constexpr bool PACKED = !SameT<E, amp_t<T>>::v;
+  constexpr int LOGU = PAIR ? 1 : 2, U = 1 << LOGU;  // four 16-byte loads in flight per lane before the first store
+  const uint32_t lane_signs = pauli_lane_signs(d.col);
+  // N elements a (at j) and b (at j ^ x) through all slots in term order; signs[u] = the sign bits of sigma_j per slot for element
+  // u (of its lower half, when packed).  Capacities 1 and 4 are unrolled; the largest walks the slots in use in a loop (the
+  // unrolled body of 32 slots does not fit the instruction cache), a slot's numbers coming from the descriptor by scalar loads.
+  auto turn = [&](auto nelem, const uint32_t* signs, E* a, E* b) {
+    constexpr int N = decltype(nelem)::v, K = PACKED ? 2 * N : N;
+    T ar[K], ai[K], br[K], bi[K];
+    uint32_t sj[K];
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+      ar[u] = a[u].x, ai[u] = a[u].y, sj[u] = signs[u];
+      br[u] = PAIR ? b[u].x : T(0), bi[u] = PAIR ? b[u].y : T(0);
+      if constexpr (PACKED) {
+        ar[N + u] = a[u].z, ai[N + u] = a[u].w, sj[N + u] = signs[u] ^ d.half;
+        br[N + u] = PAIR ? b[u].z : T(0), bi[N + u] = PAIR ? b[u].w : T(0);
+      }
+    }
+    auto one = [&](uint32_t g) {
+      const T c = d.c[g], s = d.s[g];
+      const uint32_t odd = (d.odd >> g) & 1u;
+      switch (((d.swap >> g) & 1u) | (((d.hi >> g) & 1u) << 1)) {
+        case 0: pauli_slot<0, PAIR, K>(c, s, g, odd, sj, ar, ai, br, bi); break;
+        case 1: pauli_slot<1, PAIR, K>(c, s, g, odd, sj, ar, ai, br, bi); break;
+        case 2: pauli_slot<2, PAIR, K>(c, s, g, odd, sj, ar, ai, br, bi); break;
+        default: pauli_slot<3, PAIR, K>(c, s, g, odd, sj, ar, ai, br, bi); break;
+      }
+    };
+    if constexpr (G <= 4) {
+#pragma unroll
+      for (int g = 0; g < G; ++g)
+        if ((uint32_t)g < d.count) one(g);
+    } else {
+#pragma unroll 1
+      for (uint32_t g = 0; g < d.count; ++g) one(g);
+    }
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+      a[u].x = ar[u], a[u].y = ai[u];
+      if constexpr (PAIR) b[u].x = br[u], b[u].y = bi[u];
+      if constexpr (PACKED) {
+        a[u].z = ar[N + u], a[u].w = ai[N + u];
+        if constexpr (PAIR) b[u].z = br[N + u], b[u].w = bi[N + u];
+      }
+    }
+  };
+  auto index_of = [&](uint64_t w) { return PAIR ? insert_bits<1>(w, ins) : w; };
+  constexpr uint64_t kSpan = (uint64_t)U << kStrideShift;
+  const uint64_t lo = (uint64_t)blockIdx.x * chunk;
+  const uint64_t hiw = lo + chunk < nwork ? lo + chunk : nwork;
+  uint64_t i = lo;  // (a multiple of 256 throughout: the lane id is the work index's low 8 bits)
+  for (; i + kSpan <= hiw; i += kSpan) {
+    const uint32_t span_signs = pauli_fold(d.col, i >> (kStrideShift + LOGU), kStrideShift + LOGU);
+#pragma unroll 1
+    for (uint32_t qrow = 0; qrow < (1u << (kStrideShift - 8)); ++qrow) {
+      const uint64_t w0 = i + (uint64_t)qrow * kBlock + threadIdx.x;
+      const uint32_t row_signs = span_signs ^ pauli_fold(d.col, qrow, 8) ^ lane_signs;
+      uint64_t j[U];
+      uint32_t signs[U];
+      E a[U], b[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        j[u] = index_of(w0 + ((uint64_t)u << kStrideShift));
+        signs[u] = row_signs ^ pauli_fold(d.col, u, kStrideShift);
+        a[u] = __builtin_nontemporal_load(st + j[u]);
+        if constexpr (PAIR) b[u] = __builtin_nontemporal_load(st + (j[u] ^ d.x));
+      }
+      turn(IntC<U>{}, signs, a, b);
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        __builtin_nontemporal_store(a[u], st + j[u]);
+        if constexpr (PAIR) __builtin_nontemporal_store(b[u], st + (j[u] ^ d.x));
+      }
+    }
+  }
+  for (; i < hiw; i += kBlock) {
+    const uint64_t w = i + threadIdx.x;
+    if (w < hiw) {
+      const uint64_t j = index_of(w);
+      const uint32_t signs[1] = {pauli_fold(d.col, i >> 8, 8) ^ lane_signs};
+      E a[1] = {st[j]}, b[1] = {a[0]};
+      if constexpr (PAIR) b[0] = st[j ^ d.x];
+      turn(IntC<1>{}, signs, a, b);
+      st[j] = a[0];
+      if constexpr (PAIR) st[j ^ d.x] = b[0];
+    }
   }
 }
 

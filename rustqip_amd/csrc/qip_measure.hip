@@ -657,6 +657,16 @@ static ExpectGeom expect_geom(const qip_hip_state* s, uint64_t x) {
   return g;
 }
 
+// slot `slot` of a pass's transposed z masks (k_expect_pauli's and k_pauli_rotate's `col` and `half`): bit `slot` of col[b] = the
+// amplitude-index bit behind work-index bit b lies under z
+static void pauli_columns(const ExpectGeom& g, uint32_t n, uint64_t z, uint32_t slot, uint32_t (&col)[64], uint32_t* half) {
+  if (g.packed && (z & 1ull)) *half |= 1u << slot;
+  for (uint32_t b = 0; b + g.shift + (g.pair ? 1 : 0) < n; ++b) {
+    const uint32_t pos = (g.pair && b >= g.hbit ? b + 1 : b) + g.shift;  // the amplitude-index bit behind work-index bit b
+    if ((z >> pos) & 1ull) col[b] |= 1u << slot;
+  }
+}
+
 template <typename T, int G>
 static void expect_launch_g(qip_hip_state* s, const ExpectGeom& g, const Ins& ins, const ExpectDesc& d, double* partial) {
   const dim3 grid(g.nblocks), block(kBlock);
@@ -682,11 +692,7 @@ static int expect_launch(qip_hip_state* s, const ExpectGeom& g, uint64_t x, cons
     const PauliTerm& t = terms[ids[slot]];
     if (t.ny == 1 || t.ny == 2) d.flip |= 1u << slot;
     if (t.ny & 1u) d.imag |= 1u << slot;
-    if (g.packed && (t.z & 1ull)) d.half |= 1u << slot;
-    for (uint32_t b = 0; b + g.shift + (g.pair ? 1 : 0) < s->n; ++b) {
-      const uint32_t pos = (g.pair && b >= g.hbit ? b + 1 : b) + g.shift;  // the amplitude-index bit behind work-index bit b
-      if ((t.z >> pos) & 1ull) d.col[b] |= 1u << slot;
-    }
+    pauli_columns(g, s->n, t.z, slot, d.col, &d.half);
   }
   const Ins ins = g.pair ? make_ins({g.hbit}, 0) : make_ins({}, 0);
   if (count <= 1) expect_launch_g<T, 1>(s, g, ins, d, partial);
@@ -743,6 +749,95 @@ extern "C" int qipx_state_expect_pauli(qip_hip_state* s, const uint64_t* term_st
   std::vector<PauliTerm> terms;
   QCHK(expect_reduce(s->n, term_start, qubits, paulis, count, &terms));
   return s->dtype == QIP_C64 ? expect_pauli_t<double>(s, terms, values) : expect_pauli_t<float>(s, terms, values);
+} QIP_CATCH_ALL
+
+// ---- Pauli-string rotations exp(-i theta P) in place (include/qip_hipx.h) ------------------------------------------------
+//   reduce  as above (expect_reduce), plus the angles: finite, cos and sin in double
+//   plan    maximal runs of CONSECUTIVE terms of one x mask, cut at `group` terms (rotate_plan: also all that
+//           qipx_pauli_rotation_passes runs); the terms keep their order, they do not commute in general
+//   pass    one k_pauli_rotate launch in the geometry of the expect pass of that x mask (expect_geom), queued on the stream
+// Everything is checked before the first launch; nothing is waited for.
+static void rotate_plan(const std::vector<PauliTerm>& terms, uint32_t group, std::vector<ExpectPass>* passes) {
+  passes->clear();
+  for (size_t at = 0; at < terms.size();) {
+    size_t end = at + 1;
+    while (end < terms.size() && end - at < group && terms[end].x == terms[at].x) ++end;
+    passes->push_back(ExpectPass{(uint32_t)at, (uint32_t)(end - at)});
+    at = end;
+  }
+}
+
+extern "C" int qipx_pauli_rotation_passes(uint32_t n, const uint64_t* term_start, const uint64_t* qubits, const uint8_t* paulis,
+                                          uint64_t count, uint32_t group, uint64_t* passes) try {
+  if (!passes) return fail(QIP_ERR_INVALID, "null output");
+  if (group > (uint32_t)kRotateMaxGroup) return fail(QIP_ERR_INVALID, "rotate_group is 1 to %d", kRotateMaxGroup);
+  *passes = 0;
+  if (count == 0) return QIP_OK;
+  if (count > 0xffffffffull) return fail(QIP_ERR_UNSUPPORTED, "pauli_rotations: more than 2^32 - 1 terms");
+  std::vector<PauliTerm> terms;
+  QCHK(expect_reduce(n, term_start, qubits, paulis, count, &terms));
+  std::vector<ExpectPass> plan;
+  rotate_plan(terms, group ? group : (uint32_t)kRotateGroupDefault, &plan);
+  *passes = plan.size();
+  return QIP_OK;
+} QIP_CATCH_ALL
+
+template <typename T, int G>
+static void rotate_launch_g(qip_hip_state* s, const ExpectGeom& g, const Ins& ins, const RotateDesc<T>& d) {
+  const dim3 grid(g.nblocks), block(kBlock);
+  if constexpr (std::is_same<T, float>::value) {
+    if (g.packed) {
+      if (g.pair) hipLaunchKernelGGL((k_pauli_rotate<float, G, true, f32x4>), grid, block, 0, s->stream, (f32x4*)s->cur, g.nwork, g.chunk, ins, d);
+      else hipLaunchKernelGGL((k_pauli_rotate<float, G, false, f32x4>), grid, block, 0, s->stream, (f32x4*)s->cur, g.nwork, g.chunk, ins, d);
+      return;
+    }
+  }
+  if (g.pair) hipLaunchKernelGGL((k_pauli_rotate<T, G, true>), grid, block, 0, s->stream, (amp_t<T>*)s->cur, g.nwork, g.chunk, ins, d);
+  else hipLaunchKernelGGL((k_pauli_rotate<T, G, false>), grid, block, 0, s->stream, (amp_t<T>*)s->cur, g.nwork, g.chunk, ins, d);
+}
+
+template <typename T>
+static int rotate_t(qip_hip_state* s, const std::vector<PauliTerm>& terms, const double* angles) {
+  std::vector<ExpectPass> plan;
+  rotate_plan(terms, (uint32_t)s->rotate_group, &plan);
+  for (const ExpectPass& pass : plan) {
+    const uint64_t x = terms[pass.first].x;
+    const ExpectGeom g = expect_geom<T>(s, x);
+    RotateDesc<T> d;
+    memset(&d, 0, sizeof d);
+    d.x = x >> g.shift;
+    d.count = pass.count;
+    for (uint32_t slot = 0; slot < pass.count; ++slot) {
+      const PauliTerm& t = terms[pass.first + slot];
+      const uint32_t p = (t.ny + 3u) & 3u;  // -i i^n_Y = i^p
+      if (p & 1u) d.swap |= 1u << slot;
+      if (p & 2u) d.hi |= 1u << slot;
+      if (t.ny & 1u) d.odd |= 1u << slot;
+      pauli_columns(g, s->n, t.z, slot, d.col, &d.half);
+      d.c[slot] = (T)cos(angles[pass.first + slot]);  // in double, rounded once to the state's precision
+      d.s[slot] = (T)sin(angles[pass.first + slot]);
+    }
+    const Ins ins = g.pair ? make_ins({g.hbit}, 0) : make_ins({}, 0);
+    if (pass.count <= 1) rotate_launch_g<T, 1>(s, g, ins, d);
+    else if (pass.count <= 4) rotate_launch_g<T, 4>(s, g, ins, d);
+    else rotate_launch_g<T, kRotateMaxGroup>(s, g, ins, d);  // (a loop over the slots in use: one kernel for 5 to 32 terms)
+    HIPCHK(hipGetLastError());
+  }
+  return QIP_OK;
+}
+
+extern "C" int qipx_state_apply_pauli_rotations(qip_hip_state* s, const uint64_t* term_start, const uint64_t* qubits,
+                                                const uint8_t* paulis, const double* angles, uint64_t count) try {
+  STATE_ENTER_RAW(s);
+  if (count == 0) return QIP_OK;
+  if (!angles) return fail(QIP_ERR_INVALID, "pauli_rotations: null angle array");
+  if (count > 0xffffffffull) return fail(QIP_ERR_UNSUPPORTED, "pauli_rotations: more than 2^32 - 1 terms");
+  std::vector<PauliTerm> terms;
+  QCHK(expect_reduce(s->n, term_start, qubits, paulis, count, &terms));
+  for (uint64_t t = 0; t < count; ++t)
+    if (!std::isfinite(angles[t])) return fail(QIP_ERR_INVALID, "pauli_rotations: the angle of term %llu is not finite", (unsigned long long)t);
+  if (!s->layout.empty()) QCHK(state_settle(s));  // (a relabelled state: the caller's order first, as by STATE_ENTER)
+  return s->dtype == QIP_C64 ? rotate_t<double>(s, terms, angles) : rotate_t<float>(s, terms, angles);
 } QIP_CATCH_ALL
 
 extern "C" int qip_hip_state_measure(qip_hip_state* s, const uint64_t* indices, uint32_t k,

@@ -391,6 +391,24 @@ template <typename P> class HipState {
     check(qipx_state_expect_pauli(h_, start.data(), qubits.data(), paulis.data(), terms.size(), out.data()));
     return out;
   }
+  /// psi <- exp(-i angles[t] P_t) psi for every term, in the order given (qip_hipx.h): terms as for expect_pauli.  One in-place
+  /// pass per run of consecutive terms with the same X/Y qubits; queued on the stream, returns without waiting.
+  void apply_pauli_rotations(const std::vector<std::vector<std::pair<size_t, int>>>& terms, const std::vector<double>& angles) {
+    if (angles.size() != terms.size()) throw std::invalid_argument("apply_pauli_rotations: one angle per term");
+    std::vector<uint64_t> start(1, 0), qubits;
+    std::vector<uint8_t> paulis;
+    for (const auto& term : terms) {
+      for (const auto& f : term) {
+        if (f.second < 0 || f.second > 255) throw std::invalid_argument("apply_pauli_rotations: Pauli code out of range");
+        qubits.push_back(f.first);
+        paulis.push_back(uint8_t(f.second));
+      }
+      start.push_back(qubits.size());
+    }
+    qubits.push_back(0);  // (never a null data() for a list of empty terms)
+    paulis.push_back(0);
+    check(qipx_state_apply_pauli_rotations(h_, start.data(), qubits.data(), paulis.data(), angles.data(), terms.size()));
+  }
   std::vector<double> measure_probs(const std::vector<size_t>& indices) const {
     std::vector<uint64_t> idx(indices.begin(), indices.end());
     std::vector<double> out(size_t(1) << idx.size());

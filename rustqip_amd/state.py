@@ -216,6 +216,15 @@ def expect_pauli_passes(n: int, terms, group: int = 0) -> int:
     return int(out.value)
 
 
+def pauli_rotation_passes(n: int, terms, group: int = 0) -> int:
+    """Passes over the vector HipState.apply_pauli_rotations makes for `terms` on an n-qubit state when at most `group`
+    consecutive terms of one X/Y mask share a pass (0: the default of option "rotate_group").  Host only: no device is needed."""
+    start, qubits, paulis, count = _pauli_terms(n, terms)
+    out = C.c_uint64()
+    _check(_ffi.lib.qipx_pauli_rotation_passes(int(n), start, qubits, paulis, count, int(group), C.byref(out)))
+    return int(out.value)
+
+
 def _u64_array(values: Sequence[int]):
     arr = (C.c_uint64 * len(values))(*[int(v) for v in values])
     return arr
@@ -425,6 +434,28 @@ class HipState:
         if len(c) != len(terms):
             raise CircuitError(f"{len(terms)} terms but {len(c)} coefficients")
         return float(np.dot(c, self.expect_pauli(terms)))
+
+    def apply_pauli_rotations(self, terms, angles) -> None:
+        """psi <- exp(-i angles[t] P_t) psi for every Pauli string of `terms`, in the order given (include/qip_hipx.h); the
+        term forms of expect_pauli.  One in-place pass over the vector per run of consecutive terms with the same X/Y qubits
+        (at most option "rotate_group" terms each); a batch leaves the bits of the single-term calls.  Queued on the handle's
+        stream: returns without waiting."""
+        terms = list(terms)
+        a = np.ascontiguousarray(np.asarray(angles, dtype=np.float64).reshape(-1))
+        if len(a) != len(terms):
+            raise CircuitError(f"{len(terms)} terms but {len(a)} angles")
+        start, qubits, paulis, count = _pauli_terms(self.n, terms)
+        _check(_ffi.lib.qipx_state_apply_pauli_rotations(self._h, start, qubits, paulis, a.ctypes.data_as(C.POINTER(C.c_double)), count))
+
+    def evolve(self, terms, coeffs, dt: float, steps: int = 1) -> None:
+        """First-order Trotter evolution under H = sum_t coeffs[t] * terms[t] (real coefficients) for the time steps * dt:
+        `steps` times the rotations exp(-i coeffs[t] dt P_t) in term order — the counterpart of expectation(terms, coeffs)"""
+        terms = list(terms)
+        c = np.asarray(coeffs, dtype=np.float64).reshape(-1)
+        if len(c) != len(terms):
+            raise CircuitError(f"{len(terms)} terms but {len(c)} coefficients")
+        for _ in range(int(steps)):
+            self.apply_pauli_rotations(terms, c * float(dt))
 
     def measure(self, indices: Sequence[int], measured: Optional[int] = None,
                 rand_u01: float = 0.0) -> Tuple[int, float]:
