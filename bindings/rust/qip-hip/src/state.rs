@@ -173,6 +173,53 @@ impl<P: HipPrecision> HipState<P> {
             sys_ext::qipx_state_apply_pauli_rotations(self.h, start.as_ptr(), qubits.as_ptr(), paulis.as_ptr(), angles.as_ptr(), terms.len() as u64)
         })
     }
+    /// self <- H src, or self + H src when `accumulate`, for H = sum_t coeffs[t] P_t (`include/qip_hipx.h`): terms as for
+    /// `expect_pauli`, coefficients as `(re, im)`; `src` is another state of the same size, precision and device and is not
+    /// changed.  Complete when it returns.
+    pub fn apply_pauli_sum(&mut self, src: &mut HipState<P>, terms: &[Vec<(u64, u8)>], coeffs: &[(f64, f64)], accumulate: bool) -> Result<(), HipError> {
+        assert_eq!(terms.len(), coeffs.len(), "one coefficient per term");
+        let mut start = vec![0u64];
+        let (mut qubits, mut paulis) = (Vec::new(), Vec::new());
+        for term in terms {
+            for &(q, p) in term {
+                qubits.push(q);
+                paulis.push(p);
+            }
+            start.push(qubits.len() as u64);
+        }
+        qubits.push(0);
+        paulis.push(0);
+        let mut flat: Vec<f64> = coeffs.iter().flat_map(|&(re, im)| [re, im]).collect();
+        flat.push(0.0);
+        check(unsafe {
+            sys_ext::qipx_state_apply_pauli_sum(self.h, src.h, start.as_ptr(), qubits.as_ptr(), paulis.as_ptr(), flat.as_ptr(), terms.len() as u64, accumulate as i32)
+        })
+    }
+    /// `<self| P |ket>` of Pauli strings as `(re, im)` (`include/qip_hipx.h`): raw, in double for both precisions; an empty term
+    /// gives `<self|ket>`.  Neither state is changed.  (For the Hermitian case `<psi| P |psi>` use `expect_pauli`: two `&mut` to
+    /// one state cannot be had.)
+    pub fn pauli_matrix_elements(&mut self, ket: &mut HipState<P>, terms: &[Vec<(u64, u8)>]) -> Result<Vec<(f64, f64)>, HipError> {
+        let mut start = vec![0u64];
+        let (mut qubits, mut paulis) = (Vec::new(), Vec::new());
+        for term in terms {
+            for &(q, p) in term {
+                qubits.push(q);
+                paulis.push(p);
+            }
+            start.push(qubits.len() as u64);
+        }
+        qubits.push(0);
+        paulis.push(0);
+        let mut flat = vec![0f64; 2 * terms.len()];
+        check(unsafe {
+            sys_ext::qipx_state_pauli_matrix_elements(self.h, ket.h, start.as_ptr(), qubits.as_ptr(), paulis.as_ptr(), terms.len() as u64, flat.as_mut_ptr())
+        })?;
+        Ok(flat.chunks(2).map(|c| (c[0], c[1])).collect())
+    }
+    /// `<self|other>` as `(re, im)`: `pauli_matrix_elements` with the empty term.
+    pub fn inner(&mut self, other: &mut HipState<P>) -> Result<(f64, f64), HipError> {
+        Ok(self.pauli_matrix_elements(other, &[Vec::new()])?[0])
+    }
     pub fn raw(&mut self) -> *mut sys::qip_hip_state {
         self.h
     }

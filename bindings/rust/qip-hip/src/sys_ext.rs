@@ -58,4 +58,37 @@ extern "C" {
         group: u32,
         passes: *mut u64,
     ) -> c_int;
+    /// dst <- H src (or dst + H src when `accumulate` is non-zero), H = sum_t (coeffs[2t] + i coeffs[2t+1]) P_t; the terms as
+    /// for `qipx_state_expect_pauli`.  dst != src, same n, precision and device.  Complete when it returns.
+    pub fn qipx_state_apply_pauli_sum(
+        dst: *mut qip_hip_state,
+        src: *mut qip_hip_state,
+        term_start: *const u64,
+        qubits: *const u64,
+        paulis: *const u8,
+        coeffs: *const c_double,
+        count: u64,
+        accumulate: c_int,
+    ) -> c_int;
+    /// Host only: the passes the call above makes when at most `group` terms of one X/Y mask share one (0 = the default).
+    pub fn qipx_pauli_sum_passes(
+        n: u32,
+        term_start: *const u64,
+        qubits: *const u64,
+        paulis: *const u8,
+        count: u64,
+        group: u32,
+        passes: *mut u64,
+    ) -> c_int;
+    /// values[2t] + i values[2t+1] = <bra| P_t |ket>, raw, in double for both precisions; an empty term gives <bra|ket>.
+    /// bra == ket is allowed.  Neither state is changed.
+    pub fn qipx_state_pauli_matrix_elements(
+        bra: *mut qip_hip_state,
+        ket: *mut qip_hip_state,
+        term_start: *const u64,
+        qubits: *const u64,
+        paulis: *const u8,
+        count: u64,
+        values: *mut c_double,
+    ) -> c_int;
 }

@@ -132,6 +132,72 @@ int qipx_state_apply_pauli_rotations(qip_hip_state* s, const uint64_t* term_star
 int qipx_pauli_rotation_passes(uint32_t n, const uint64_t* term_start, const uint64_t* qubits, const uint8_t* paulis,
                                uint64_t count, uint32_t group, uint64_t* passes);
 
+/* A Pauli sum applied to a second state.  (Added without a change of QIPX_ABI_VERSION: purely additive again.)
+ *
+ * dst <- H src, or dst <- dst + H src when `accumulate` is non-zero, for H = sum_t c_t P_t with complex coefficients
+ * c_t = coeffs[2t] + i coeffs[2t+1].  The terms are given exactly as for qipx_state_expect_pauli above (the same arrays, the same
+ * codes, qubit q = index bit n-1-q) and are checked by the same code with the same messages.  With x, z, n_Y as there,
+ *   dst[j] = (accumulate ? dst[j] : 0) + sum_t c_t * i^n_Y,t * (-1)^popcount((j ^ x_t) & z_t) * src[j ^ x_t].
+ * H need not be Hermitian and nothing is normalised.  This is the step of the adjoint gradient (lambda = H psi), of Lanczos and
+ * Krylov iterations, of an imaginary-time step and of <H^2>.
+ *
+ * Cost.  The terms are sorted by x mask (stably); the terms of one x mask share passes, at most "sum_group" terms per pass: one
+ * kernel launch per pass, which reads `src` once and reads and writes `dst` once (the first pass of a call that does not
+ * accumulate stores without reading `dst`).  No atomics.
+ *
+ * Arithmetic.  Everything is formed in the state's precision (u = 2^-53, 2^-24), without fused multiply-add.  k_t = c_t * i^n_Y,t
+ * (a swap and sign flips, exact) is rounded once to that precision on the host.  Per amplitude a pass forms the signed
+ * coefficient sum w = sum of (+-)k_t over its terms, in term order starting from +0, one addition per component and term; then the
+ * complex product p = w * src[j ^ x] as re = fl(fl(wr sr) - fl(wi si)), im = fl(fl(wr si) + fl(wi sr)); then stores p (first pass
+ * of a call that does not accumulate) or fl(dst[j] + p) per component.  To first order in u the error of an amplitude is within
+ *   (m + 3) u * sum_t |c_t| |src[j ^ x_t]|  +  P u * (sum_t |c_t| |src[j ^ x_t]| + |dst_old[j]|)
+ * for P passes of at most m terms each (m + P <= count + 1).  The result depends on the call only — same call, same bits — but
+ * NOT only on the terms: another "sum_group", or another order of the terms, adds in another order and may differ by rounding.
+ *
+ * Calling contract.  Both handles are put in the caller's order on entry (option "tile_relabel" = 3), the work queued on `src` is
+ * waited for, the passes run on `dst`'s stream, and THE CALL IS COMPLETE WHEN IT RETURNS, as qip_hip_state_copy_from is: the caller
+ * may change `src` at once.  `src` is not changed.  count == 0 sets dst to zero, or leaves it as it is when accumulating (null
+ * arrays allowed).  Each of these is refused with a message before anything is queued, `dst` untouched: a null handle
+ * (QIP_ERR_INVALID, there is no host fall-back); a handle that is unusable after a failed relabelled batch (QIP_ERR_DEVICE);
+ * dst == src (QIP_ERR_INVALID: later passes need the source intact); handles that differ in n or dtype (QIP_ERR_INVALID) or live
+ * on different devices (QIP_ERR_UNSUPPORTED); with count > 0 a null array, a non-finite coefficient (the message names the term)
+ * or any term error of qipx_state_expect_pauli (QIP_ERR_INVALID); more than 2^32 - 1 terms (QIP_ERR_UNSUPPORTED).
+ *
+ * State option "sum_group" (of `dst`): the most terms per pass, 1 to 32, anything else is refused with QIP_ERR_INVALID.
+ * Default 16: the largest of 1, 4, 16, 32 terms whose pass stayed within 1.5x of the single-term pass in the run recorded in
+ * profiles/adjoint_gradient.md (tools/bench_adjoint.py, n = 30, both precisions: 16 terms 1.11x / 1.08x, 32 terms 1.43x / 1.65x;
+ * a storing pass of up to 16 terms costs what a rotation pass costs, an accumulating one 1.5x: three vectors against two). */
+int qipx_state_apply_pauli_sum(qip_hip_state* dst, qip_hip_state* src, const uint64_t* term_start, const uint64_t* qubits,
+                               const uint8_t* paulis, const double* coeffs, uint64_t count, int accumulate);
+
+/* Host only, no device needed: the number of passes the call above makes for these terms on an n-qubit state when at most
+ * `group` terms share a pass (group = 0: the default of "sum_group"; above 32: QIP_ERR_INVALID).  The terms are checked as
+ * above; count == 0 gives 0 passes.  It runs the grouping code the call itself runs. */
+int qipx_pauli_sum_passes(uint32_t n, const uint64_t* term_start, const uint64_t* qubits, const uint8_t* paulis,
+                          uint64_t count, uint32_t group, uint64_t* passes);
+
+/* Pauli matrix elements between two states.  (Purely additive again.)
+ *
+ * values[2t] + i values[2t+1] = <bra| P_t |ket>
+ *                             = sum_j conj(bra[j]) * i^n_Y * (-1)^popcount((j ^ x) & z) * ket[j ^ x],     t < count,
+ * the terms as for qipx_state_expect_pauli.  The value is raw: it is not divided by any norm.  An empty term (and a term of I
+ * factors only) gives the inner product <bra|ket>.  bra == ket is allowed: the Hermitian case, whose real part is the value of
+ * qipx_state_expect_pauli up to rounding (that call and its bits are untouched by this one: it has its own kernel).
+ *
+ * Precision.  Products and sums are formed in double for both precisions; f32 amplitudes are widened before the first product.
+ * Determinism and reproducibility are those of qipx_state_expect_pauli: per-block partial sums in `ket`'s reduction scratch,
+ * added on the host in block order, no atomics; values[2t], values[2t+1] depend on the two states and on term t only, so a batch
+ * equals its single-term calls bit for bit under any "expect_group".
+ *
+ * Cost.  The terms are sorted by x mask (stably) and the terms of one x mask share passes over both vectors, at most
+ * min("expect_group" of `ket`, 16) terms per pass (the kernel keeps two running sums per term).
+ *
+ * Neither state is changed.  Both handles are put in the caller's order on entry; the call is ordered after the work queued on
+ * both handles and complete when it returns.  count == 0 returns QIP_OK (null arrays allowed).  The handles are checked as by the
+ * call above (bra == ket excepted); with count > 0 a null array or any term error of qipx_state_expect_pauli is QIP_ERR_INVALID. */
+int qipx_state_pauli_matrix_elements(qip_hip_state* bra, qip_hip_state* ket, const uint64_t* term_start, const uint64_t* qubits,
+                                     const uint8_t* paulis, uint64_t count, double* values);
+
 #ifdef __cplusplus
 }
 #endif

@@ -168,6 +168,9 @@ EXT_SIGNATURES = {
     "qipx_expect_pauli_passes": (_int, [_u32, _u64p, _u64p, C.POINTER(C.c_uint8), _u64, _u32, _u64p]),
     "qipx_state_apply_pauli_rotations": (_int, [_statep, _u64p, _u64p, C.POINTER(C.c_uint8), _dblp, _u64]),
     "qipx_pauli_rotation_passes": (_int, [_u32, _u64p, _u64p, C.POINTER(C.c_uint8), _u64, _u32, _u64p]),
+    "qipx_state_apply_pauli_sum": (_int, [_statep, _statep, _u64p, _u64p, C.POINTER(C.c_uint8), _dblp, _u64, _int]),
+    "qipx_pauli_sum_passes": (_int, [_u32, _u64p, _u64p, C.POINTER(C.c_uint8), _u64, _u32, _u64p]),
+    "qipx_state_pauli_matrix_elements": (_int, [_statep, _statep, _u64p, _u64p, C.POINTER(C.c_uint8), _u64, _dblp]),
 }
 
 

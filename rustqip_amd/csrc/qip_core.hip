@@ -580,6 +580,10 @@ extern "C" int qip_hip_state_set_option(qip_hip_state* s, const char* key, int64
     if (value < 1 || value > kRotateMaxGroup) return fail(QIP_ERR_INVALID, "rotate_group is 1 to %d", kRotateMaxGroup);
     s->rotate_group = value;
   }
+  else if (!strcmp(key, "sum_group")) {
+    if (value < 1 || value > kSumMaxGroup) return fail(QIP_ERR_INVALID, "sum_group is 1 to %d", kSumMaxGroup);
+    s->sum_group = value;
+  }
 #ifdef QIP_HIP_TUNING
   else if (!strcmp(key, "lowbit_shuffle")) s->lowbit_shuffle = value;
   else if (!strcmp(key, "packed_f32")) s->packed_f32 = value;

@@ -142,6 +142,8 @@ bool sparse_tile_applies(const qip_hip_state* s, const Plan& p, const FlatOp& f)
 static constexpr int64_t kExpectGroupDefault = 16;
 // qipx_state_apply_pauli_rotations: the default of option "rotate_group" (include/qip_hipx.h says which measurement chose it)
 static constexpr int64_t kRotateGroupDefault = 16;
+// qipx_state_apply_pauli_sum: the default of option "sum_group" (include/qip_hipx.h says which measurement chose it)
+static constexpr int64_t kSumGroupDefault = 16;
 
 struct ProfRec {
   int cls;
@@ -174,6 +176,7 @@ struct qip_hip_state {
   int64_t sample_slab = 1ll << 22;  // option "sample_slab": samples per slab
   int64_t expect_group = kExpectGroupDefault;  // option "expect_group": most terms of qipx_state_expect_pauli that share a pass
   int64_t rotate_group = kRotateGroupDefault;  // option "rotate_group": most terms of qipx_state_apply_pauli_rotations that share a pass
+  int64_t sum_group = kSumGroupDefault;  // option "sum_group": most terms of qipx_state_apply_pauli_sum that share a pass
   // options
   int64_t force_generic = 0;
   int64_t profile = 0;

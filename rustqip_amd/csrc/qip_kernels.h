@@ -3125,6 +3125,245 @@ __global__ __launch_bounds__(kBlock) void k_pauli_rotate(E* __restrict__ st, uin
   }
 }
 
+// ---- a Pauli sum applied to a second state: dst (+)= (sum_t c_t P_t) src (qipx_state_apply_pauli_sum, include/qip_hipx.h) -------
+// (P src)[j] = i^n_Y sigma_{j^x} src[j ^ x] has one partner per amplitude, so the terms of one x mask share a pass in
+// k_pauli_rotate's geometry (PAIR, PACKED, `ins`, `chunk`, spans and rows as there): the lane that owns the pair (j, j ^ x) loads
+// both source amplitudes, forms for each of them the signed coefficient sum
+//   w(j) = sum_g sigma_g(j ^ x) k_g,     w(j ^ x) = sum_g sigma_g(j) k_g,     k_g = c_g i^n_Y,g rounded once to T on the host,
+// slot after slot in term order starting from +0 (a sign flip and an add per component, slot and amplitude), then one complex
+// product per amplitude, re = fl(fl(wr sr) - fl(wi si)), im = fl(fl(wr si) + fl(wi sr)), never fused, and stores it (FIRST: the
+// destination is not read) or adds it to the destination's amplitude, one rounding per component.  src is read once, dst read
+// and written once; no LDS, no atomics.  sigma_j comes from the transposed z masks as in k_pauli_rotate, sigma_{j^x} = sigma_j (-1)^n_Y.
+//   odd    bit g: n_Y odd
+//   half   packed Complex<f32>: bit 0 of slot g's z mask, as in ExpectDesc
+constexpr int kSumMaxGroup = 32;
+template <typename T> struct SumDesc {
+  uint64_t x;      // the pass's x mask, in elements
+  uint32_t count;  // slots in use
+  uint32_t odd, half;
+  uint32_t col[64];
+  T kr[kSumMaxGroup], ki[kSumMaxGroup];
+};
+
+// (dr, di) <- [FIRST ? 0 : (dr, di)] + (wr, wi) * (sr, si)
+template <bool FIRST, typename T> __device__ __forceinline__ void pauli_sum_put(T wr, T wi, T sr, T si, T& dr, T& di) {
+  const T pr = wr * sr - wi * si, pi = wr * si + wi * sr;
+  dr = FIRST ? pr : dr + pr;
+  di = FIRST ? pi : di + pi;
+}
+
+template <typename T, int G, bool PAIR, bool FIRST, typename E = amp_t<T>>
+__global__ __launch_bounds__(kBlock) void k_pauli_sum(E* __restrict__ dst, const E* __restrict__ src, uint64_t nwork, uint64_t chunk,
+                                                      Ins ins, SumDesc<T> d) {
+  constexpr bool PACKED = !SameT<E, amp_t<T>>::v;
+  constexpr int LOGU = PAIR ? 1 : 2, U = 1 << LOGU;  // k_pauli_rotate's loads in flight for the source
+  const uint32_t lane_signs = pauli_lane_signs(d.col);
+  // N source elements a (at j) and b (at j ^ x) into the destination elements da (at j) and db (at j ^ x); signs[u] = the sign
+  // bits of sigma_j per slot for element u (of its lower half, when packed).  Capacities 1 and 4 are unrolled, the largest walks
+  // the slots in use in a loop, a slot's coefficient coming from the descriptor by scalar loads (as k_pauli_rotate does).
+  auto turn = [&](auto nelem, const uint32_t* signs, const E* a, const E* b, E* da, E* db) {
+    constexpr int N = decltype(nelem)::v, K = PACKED ? 2 * N : N;
+    uint32_t sj[K];
+    T wbr[K], wbi[K], war[K], wai[K];  // wb: sum of sigma_g(j) k_g, for the amplitude at j ^ x (at j when x = 0); wa: for the one at j
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      sj[k] = k < N ? signs[k] : signs[k - N] ^ d.half;
+      wbr[k] = wbi[k] = war[k] = wai[k] = T(0);
+    }
+    auto one = [&](uint32_t g) {
+      const T kr = d.kr[g], ki = d.ki[g];
+      const uint32_t odd = (d.odd >> g) & 1u;
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const uint32_t bit = (sj[k] >> g) & 1u;
+        wbr[k] += flip_sign(kr, bit), wbi[k] += flip_sign(ki, bit);
+        if constexpr (PAIR) war[k] += flip_sign(kr, bit ^ odd), wai[k] += flip_sign(ki, bit ^ odd);
+      }
+    };
+    if constexpr (G <= 4) {
+#pragma unroll
+      for (int g = 0; g < G; ++g)
+        if ((uint32_t)g < d.count) one(g);
+    } else {
+#pragma unroll 1
+      for (uint32_t g = 0; g < d.count; ++g) one(g);
+    }
+    // one amplitude: d <- [d +] w * s through scalars (a vector's component does not bind to a reference)
+    auto put = [&](T wr, T wi, T sr, T si, T dr, T di, T* outr, T* outi) {
+      pauli_sum_put<FIRST>(wr, wi, sr, si, dr, di);
+      *outr = dr, *outi = di;
+    };
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+      T r0, i0, r1 = T(0), i1 = T(0);
+      if constexpr (PAIR) {
+        put(war[u], wai[u], b[u].x, b[u].y, da[u].x, da[u].y, &r0, &i0);
+        if constexpr (PACKED) put(war[N + u], wai[N + u], b[u].z, b[u].w, da[u].z, da[u].w, &r1, &i1);
+        da[u].x = r0, da[u].y = i0;
+        if constexpr (PACKED) da[u].z = r1, da[u].w = i1;
+        put(wbr[u], wbi[u], a[u].x, a[u].y, db[u].x, db[u].y, &r0, &i0);
+        if constexpr (PACKED) put(wbr[N + u], wbi[N + u], a[u].z, a[u].w, db[u].z, db[u].w, &r1, &i1);
+        db[u].x = r0, db[u].y = i0;
+        if constexpr (PACKED) db[u].z = r1, db[u].w = i1;
+      } else {
+        put(wbr[u], wbi[u], a[u].x, a[u].y, da[u].x, da[u].y, &r0, &i0);
+        if constexpr (PACKED) put(wbr[N + u], wbi[N + u], a[u].z, a[u].w, da[u].z, da[u].w, &r1, &i1);
+        da[u].x = r0, da[u].y = i0;
+        if constexpr (PACKED) da[u].z = r1, da[u].w = i1;
+      }
+    }
+  };
+  auto index_of = [&](uint64_t w) { return PAIR ? insert_bits<1>(w, ins) : w; };
+  constexpr uint64_t kSpan = (uint64_t)U << kStrideShift;
+  const uint64_t lo = (uint64_t)blockIdx.x * chunk;
+  const uint64_t hiw = lo + chunk < nwork ? lo + chunk : nwork;
+  uint64_t i = lo;  // (a multiple of 256 throughout: the lane id is the work index's low 8 bits)
+  for (; i + kSpan <= hiw; i += kSpan) {
+    const uint32_t span_signs = pauli_fold(d.col, i >> (kStrideShift + LOGU), kStrideShift + LOGU);
+#pragma unroll 1
+    for (uint32_t qrow = 0; qrow < (1u << (kStrideShift - 8)); ++qrow) {
+      const uint64_t w0 = i + (uint64_t)qrow * kBlock + threadIdx.x;
+      const uint32_t row_signs = span_signs ^ pauli_fold(d.col, qrow, 8) ^ lane_signs;
+      uint64_t j[U];
+      uint32_t signs[U];
+      E a[U], b[U], da[U], db[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        j[u] = index_of(w0 + ((uint64_t)u << kStrideShift));
+        signs[u] = row_signs ^ pauli_fold(d.col, u, kStrideShift);
+        a[u] = __builtin_nontemporal_load(src + j[u]);
+        if constexpr (PAIR) b[u] = __builtin_nontemporal_load(src + (j[u] ^ d.x));
+        else b[u] = a[u];
+        if constexpr (!FIRST) {
+          da[u] = __builtin_nontemporal_load(dst + j[u]);
+          if constexpr (PAIR) db[u] = __builtin_nontemporal_load(dst + (j[u] ^ d.x));
+        }
+      }
+      turn(IntC<U>{}, signs, a, b, da, db);
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        __builtin_nontemporal_store(da[u], dst + j[u]);
+        if constexpr (PAIR) __builtin_nontemporal_store(db[u], dst + (j[u] ^ d.x));
+      }
+    }
+  }
+  for (; i < hiw; i += kBlock) {
+    const uint64_t w = i + threadIdx.x;
+    if (w < hiw) {
+      const uint64_t j = index_of(w);
+      const uint32_t signs[1] = {pauli_fold(d.col, i >> 8, 8) ^ lane_signs};
+      E a[1] = {src[j]}, b[1] = {a[0]}, da[1], db[1];
+      if constexpr (PAIR) b[0] = src[j ^ d.x];
+      if constexpr (!FIRST) {
+        da[0] = dst[j];
+        if constexpr (PAIR) db[0] = dst[j ^ d.x];
+      }
+      turn(IntC<1>{}, signs, a, b, da, db);
+      dst[j] = da[0];
+      if constexpr (PAIR) dst[j ^ d.x] = db[0];
+    }
+  }
+}
+
+// ---- Pauli matrix elements between two states: <bra| P_t |ket> (qipx_state_pauli_matrix_elements, include/qip_hipx.h) --------
+// sum_j conj(bra[j]) i^n_Y sigma_{j^x} ket[j ^ x], the terms of one x mask in one pass over both vectors in k_expect_pauli's
+// geometry.  The two members of a pair (j, j ^ x) give
+//   sigma_{j^x} A + sigma_j B = sigma_j ((-1)^n_Y A + B),     A = conj(bra[j]) ket[j ^ x],     B = conj(bra[j ^ x]) ket[j],
+// so a pair costs two complex products, S = B + A and D = B - A once, and per slot a choice (n_Y odd: D), a sign and one complex
+// add to the slot's running sum; x = 0 takes conj(bra[j]) ket[j].  i^n_Y is applied by the host to the finished sum (exact).
+// Everything is widened to double before the first product.  The signs are handled as in k_expect_pauli (wave-uniform share per
+// addend, the lane's share once at the end), and as there a slot sees the same addends in the same order for every capacity G
+// and whatever its company.  partial[(2 g + c) * gridDim.x + blockIdx.x], c = 0 the real and 1 the imaginary part; no atomics.
+constexpr int kMelemMaxGroup = 16;  // (two running sums per slot)
+struct MelemDesc {
+  uint64_t x;      // the pass's x mask, in elements
+  uint32_t count;  // slots in use
+  uint32_t odd, half;
+  uint32_t col[64];
+};
+
+template <typename T, int G, bool PAIR, typename E = amp_t<T>>
+__global__ __launch_bounds__(kBlock) void k_pauli_melem(const E* __restrict__ bra, const E* __restrict__ ket, uint64_t nwork,
+                                                        uint64_t chunk, Ins ins, MelemDesc d, double* __restrict__ partial) {
+  constexpr bool PACKED = !SameT<E, amp_t<T>>::v;
+  __shared__ double smem[kBlock / 64];
+  double accr[G], acci[G];
+#pragma unroll
+  for (int g = 0; g < G; ++g) accr[g] = acci[g] = 0.0;
+  auto fold = [&](uint64_t v, uint32_t b) { return pauli_fold(d.col, v, b); };
+  const uint32_t lane_signs = pauli_lane_signs(d.col);
+  // one amplitude pair: (pr, pi) = bra at j, (qr, qi) = bra at j ^ x, (ar, ai) = ket at j, (br, bi) = ket at j ^ x
+  auto add = [&](uint32_t signs, double pr, double pi, double qr, double qi, double ar, double ai, double br, double bi) {
+    double sr, si, dr = 0.0, di = 0.0;
+    if constexpr (PAIR) {
+      const double Ar = pr * br + pi * bi, Ai = pr * bi - pi * br;  // conj(bra[j]) ket[j ^ x]
+      const double Br = qr * ar + qi * ai, Bi = qr * ai - qi * ar;  // conj(bra[j ^ x]) ket[j]
+      sr = Br + Ar, si = Bi + Ai, dr = Br - Ar, di = Bi - Ai;
+    } else {
+      sr = pr * ar + pi * ai, si = pr * ai - pi * ar;
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      const bool odd = PAIR && ((d.odd >> g) & 1u);
+      const uint64_t sign = (uint64_t)((signs >> g) & 1u) << 63;
+      accr[g] += __longlong_as_double(__double_as_longlong(odd ? dr : sr) ^ (long long)sign);
+      acci[g] += __longlong_as_double(__double_as_longlong(odd ? di : si) ^ (long long)sign);
+    }
+  };
+  // p = bra at j, q = bra at j ^ x, a = ket at j, b = ket at j ^ x; `signs` = the wave-uniform share of the sign bits at j
+  auto take = [&](uint32_t signs, E p, E q, E a, E b) {
+    add(signs, p.x, p.y, q.x, q.y, a.x, a.y, b.x, b.y);
+    if constexpr (PACKED) add(signs ^ d.half, p.z, p.w, q.z, q.w, a.z, a.w, b.z, b.w);
+  };
+  auto index_of = [&](uint64_t w) { return PAIR ? insert_bits<1>(w, ins) : w; };
+  constexpr int LOGU = PAIR ? 1 : 2, U = 1 << LOGU;
+  constexpr uint64_t kSpan = (uint64_t)U << kStrideShift;
+  const uint64_t lo = (uint64_t)blockIdx.x * chunk;
+  const uint64_t hi = lo + chunk < nwork ? lo + chunk : nwork;
+  uint64_t i = lo;  // (a multiple of 256 throughout: the lane id is the work index's low 8 bits)
+  for (; i + kSpan <= hi; i += kSpan) {
+    const uint32_t span_signs = fold(i >> (kStrideShift + LOGU), kStrideShift + LOGU);
+#pragma unroll 1
+    for (uint32_t qrow = 0; qrow < (1u << (kStrideShift - 8)); ++qrow) {
+      const uint64_t w0 = i + (uint64_t)qrow * kBlock + threadIdx.x;
+      const uint32_t row_signs = span_signs ^ fold(qrow, 8);
+      E p[U], q[U], a[U], b[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const uint64_t j = index_of(w0 + ((uint64_t)u << kStrideShift));
+        p[u] = __builtin_nontemporal_load(bra + j);
+        a[u] = __builtin_nontemporal_load(ket + j);
+        if constexpr (PAIR) {
+          q[u] = __builtin_nontemporal_load(bra + (j ^ d.x));
+          b[u] = __builtin_nontemporal_load(ket + (j ^ d.x));
+        } else {
+          q[u] = p[u], b[u] = a[u];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) take(row_signs ^ fold(u, kStrideShift), p[u], q[u], a[u], b[u]);
+    }
+  }
+  for (; i < hi; i += kBlock) {
+    const uint64_t w = i + threadIdx.x;
+    if (w < hi) {
+      const uint64_t j = index_of(w);
+      const E p = bra[j], a = ket[j];
+      take(fold(i >> 8, 8), p, PAIR ? bra[j ^ d.x] : p, a, PAIR ? ket[j ^ d.x] : a);
+    }
+  }
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const bool neg = (lane_signs >> g) & 1u;
+    const double tr = block_reduce_sum(neg ? -accr[g] : accr[g], smem);
+    const double ti = block_reduce_sum(neg ? -acci[g] : acci[g], smem);
+    if (threadIdx.x == 0 && (uint32_t)g < d.count) {
+      partial[(uint64_t)(2 * g) * gridDim.x + blockIdx.x] = tr;
+      partial[(uint64_t)(2 * g + 1) * gridDim.x + blockIdx.x] = ti;
+    }
+  }
+}
+
 // Two states compared amplitude by amplitude over the whole vector (qip_hip_state_max_abs_diff: how far a state is from a
 // reference copy): partial[2 b] = max |a_i - b_i| over block b's share, partial[2 b + 1] = number of amplitudes whose
 // components are not IEEE-equal (NaNs count as different).  Grid-stride, one coalesced pass over both vectors.

@@ -840,6 +840,202 @@ extern "C" int qipx_state_apply_pauli_rotations(qip_hip_state* s, const uint64_t
   return s->dtype == QIP_C64 ? rotate_t<double>(s, terms, angles) : rotate_t<float>(s, terms, angles);
 } QIP_CATCH_ALL
 
+// ---- two states and Pauli strings: dst (+)= (sum_t c_t P_t) src and <bra| P_t |ket> (include/qip_hipx.h) ---------------------
+//   meet    the two handles as copy_from and max_abs_diff meet theirs (pair_meet: the checks; pair_settle: the caller's order and
+//           the other handle's stream drained), everything that can refuse the call before anything is queued
+//   reduce  as above (expect_reduce)
+//   plan    expect_plan: sorted stably by x mask, each run cut at `group` terms (also all that qipx_pauli_sum_passes runs)
+//   pass    one k_pauli_sum / k_pauli_melem launch in the geometry of the expect pass of that x mask (expect_geom)
+// Both calls are complete when they return.
+static int pair_meet(const char* what, qip_hip_state* own, qip_hip_state* other) {
+  if (!other) return fail(QIP_ERR_INVALID, "%s: null state handle", what);
+  if (other->poisoned) return fail(QIP_ERR_DEVICE, "%s: the other state is unusable: %s", what, other->poison_msg.c_str());
+  if (own->n != other->n || own->dtype != other->dtype) return fail(QIP_ERR_INVALID, "%s: states differ in size or precision", what);
+  if (own->device != other->device) return fail(QIP_ERR_UNSUPPORTED, "%s: states live on different devices", what);
+  return QIP_OK;
+}
+
+// both in the caller's order, and everything queued on `other` has landed: the work then runs on `own`'s stream
+static int pair_settle(qip_hip_state* own, qip_hip_state* other) {
+  if (!own->layout.empty()) QCHK(state_settle(own));
+  if (other != own) {
+    if (!other->layout.empty()) QCHK(state_settle(other));
+    HIPCHK(hipStreamSynchronize(other->stream));
+  }
+  return QIP_OK;
+}
+
+extern "C" int qipx_pauli_sum_passes(uint32_t n, const uint64_t* term_start, const uint64_t* qubits, const uint8_t* paulis,
+                                     uint64_t count, uint32_t group, uint64_t* passes) try {
+  if (!passes) return fail(QIP_ERR_INVALID, "null output");
+  if (group > (uint32_t)kSumMaxGroup) return fail(QIP_ERR_INVALID, "sum_group is 1 to %d", kSumMaxGroup);
+  *passes = 0;
+  if (count == 0) return QIP_OK;
+  if (count > 0xffffffffull) return fail(QIP_ERR_UNSUPPORTED, "pauli_sum: more than 2^32 - 1 terms");
+  std::vector<PauliTerm> terms;
+  QCHK(expect_reduce(n, term_start, qubits, paulis, count, &terms));
+  std::vector<uint32_t> order;
+  std::vector<ExpectPass> plan;
+  expect_plan(terms, group ? group : (uint32_t)kSumGroupDefault, &order, &plan);
+  *passes = plan.size();
+  return QIP_OK;
+} QIP_CATCH_ALL
+
+template <typename T, int G, bool FIRST>
+static void sum_launch_g(qip_hip_state* dst, const qip_hip_state* src, const ExpectGeom& g, const Ins& ins, const SumDesc<T>& d) {
+  const dim3 grid(g.nblocks), block(kBlock);
+  if constexpr (std::is_same<T, float>::value) {
+    if (g.packed) {
+      if (g.pair) hipLaunchKernelGGL((k_pauli_sum<float, G, true, FIRST, f32x4>), grid, block, 0, dst->stream, (f32x4*)dst->cur, (const f32x4*)src->cur, g.nwork, g.chunk, ins, d);
+      else hipLaunchKernelGGL((k_pauli_sum<float, G, false, FIRST, f32x4>), grid, block, 0, dst->stream, (f32x4*)dst->cur, (const f32x4*)src->cur, g.nwork, g.chunk, ins, d);
+      return;
+    }
+  }
+  if (g.pair) hipLaunchKernelGGL((k_pauli_sum<T, G, true, FIRST>), grid, block, 0, dst->stream, (amp_t<T>*)dst->cur, (const amp_t<T>*)src->cur, g.nwork, g.chunk, ins, d);
+  else hipLaunchKernelGGL((k_pauli_sum<T, G, false, FIRST>), grid, block, 0, dst->stream, (amp_t<T>*)dst->cur, (const amp_t<T>*)src->cur, g.nwork, g.chunk, ins, d);
+}
+
+template <typename T, bool FIRST>
+static void sum_launch(qip_hip_state* dst, const qip_hip_state* src, const ExpectGeom& g, const Ins& ins, const SumDesc<T>& d) {
+  if (d.count <= 1) sum_launch_g<T, 1, FIRST>(dst, src, g, ins, d);
+  else if (d.count <= 4) sum_launch_g<T, 4, FIRST>(dst, src, g, ins, d);
+  else sum_launch_g<T, kSumMaxGroup, FIRST>(dst, src, g, ins, d);  // (a loop over the slots in use: one kernel for 5 to 32 terms)
+}
+
+template <typename T>
+static int pauli_sum_t(qip_hip_state* dst, const qip_hip_state* src, const std::vector<PauliTerm>& terms, const double* coeffs,
+                       bool accumulate) {
+  std::vector<uint32_t> order;
+  std::vector<ExpectPass> plan;
+  expect_plan(terms, (uint32_t)dst->sum_group, &order, &plan);
+  if (plan.empty() && !accumulate) HIPCHK(hipMemsetAsync(dst->cur, 0, dst->namps * dst->amp_bytes, dst->stream));
+  bool first = !accumulate;
+  for (const ExpectPass& pass : plan) {
+    const uint64_t x = terms[order[pass.first]].x;
+    const ExpectGeom g = expect_geom<T>(dst, x);
+    SumDesc<T> d;
+    memset(&d, 0, sizeof d);
+    d.x = x >> g.shift;
+    d.count = pass.count;
+    for (uint32_t slot = 0; slot < pass.count; ++slot) {
+      const uint32_t id = order[pass.first + slot];
+      const PauliTerm& t = terms[id];
+      if (t.ny & 1u) d.odd |= 1u << slot;
+      pauli_columns(g, dst->n, t.z, slot, d.col, &d.half);
+      const double cr = coeffs[2 * (size_t)id], ci = coeffs[2 * (size_t)id + 1];
+      // k = c i^n_Y: a swap and sign flips in double, then rounded once to the state's precision
+      d.kr[slot] = (T)(t.ny == 0 ? cr : t.ny == 1 ? -ci : t.ny == 2 ? -cr : ci);
+      d.ki[slot] = (T)(t.ny == 0 ? ci : t.ny == 1 ? cr : t.ny == 2 ? -ci : -cr);
+    }
+    const Ins ins = g.pair ? make_ins({g.hbit}, 0) : make_ins({}, 0);
+    if (first) sum_launch<T, true>(dst, src, g, ins, d);
+    else sum_launch<T, false>(dst, src, g, ins, d);
+    HIPCHK(hipGetLastError());
+    first = false;
+  }
+  HIPCHK(hipStreamSynchronize(dst->stream));  // complete on return: the caller may touch `src` at once
+  return QIP_OK;
+}
+
+extern "C" int qipx_state_apply_pauli_sum(qip_hip_state* dst, qip_hip_state* src, const uint64_t* term_start, const uint64_t* qubits,
+                                          const uint8_t* paulis, const double* coeffs, uint64_t count, int accumulate) try {
+  STATE_ENTER_RAW(dst);
+  QCHK(pair_meet("pauli_sum", dst, src));
+  if (dst == src) return fail(QIP_ERR_INVALID, "pauli_sum: the destination is the source (later passes need the source intact)");
+  std::vector<PauliTerm> terms;
+  if (count > 0) {
+    if (!coeffs) return fail(QIP_ERR_INVALID, "pauli_sum: null coefficient array");
+    if (count > 0xffffffffull) return fail(QIP_ERR_UNSUPPORTED, "pauli_sum: more than 2^32 - 1 terms");
+    QCHK(expect_reduce(dst->n, term_start, qubits, paulis, count, &terms));
+    for (uint64_t t = 0; t < count; ++t)
+      if (!std::isfinite(coeffs[2 * t]) || !std::isfinite(coeffs[2 * t + 1]))
+        return fail(QIP_ERR_INVALID, "pauli_sum: the coefficient of term %llu is not finite", (unsigned long long)t);
+  }
+  QCHK(pair_settle(dst, src));
+  return dst->dtype == QIP_C64 ? pauli_sum_t<double>(dst, src, terms, coeffs, accumulate != 0)
+                               : pauli_sum_t<float>(dst, src, terms, coeffs, accumulate != 0);
+} QIP_CATCH_ALL
+
+template <typename T, int G>
+static void melem_launch_g(qip_hip_state* ket, const qip_hip_state* bra, const ExpectGeom& g, const Ins& ins, const MelemDesc& d,
+                           double* partial) {
+  const dim3 grid(g.nblocks), block(kBlock);
+  if (g.packed && g.pair)
+    hipLaunchKernelGGL((k_pauli_melem<float, G, true, f32x4>), grid, block, 0, ket->stream, (const f32x4*)bra->cur, (const f32x4*)ket->cur, g.nwork, g.chunk, ins, d, partial);
+  else if (g.packed)
+    hipLaunchKernelGGL((k_pauli_melem<float, G, false, f32x4>), grid, block, 0, ket->stream, (const f32x4*)bra->cur, (const f32x4*)ket->cur, g.nwork, g.chunk, ins, d, partial);
+  else if (g.pair)
+    hipLaunchKernelGGL((k_pauli_melem<T, G, true>), grid, block, 0, ket->stream, (const amp_t<T>*)bra->cur, (const amp_t<T>*)ket->cur, g.nwork, g.chunk, ins, d, partial);
+  else
+    hipLaunchKernelGGL((k_pauli_melem<T, G, false>), grid, block, 0, ket->stream, (const amp_t<T>*)bra->cur, (const amp_t<T>*)ket->cur, g.nwork, g.chunk, ins, d, partial);
+}
+
+template <typename T>
+static int pauli_melem_t(qip_hip_state* ket, const qip_hip_state* bra, const std::vector<PauliTerm>& terms, double* values) {
+  std::vector<uint32_t> order;
+  std::vector<ExpectPass> plan;
+  expect_plan(terms, (uint32_t)std::min<int64_t>(ket->expect_group, kMelemMaxGroup), &order, &plan);
+  std::vector<ExpectGeom> geom(plan.size());
+  size_t total = 0;
+  for (size_t p = 0; p < plan.size(); ++p) {
+    geom[p] = expect_geom<T>(ket, terms[order[plan[p].first]].x);
+    total += 2 * (size_t)plan[p].count * geom[p].nblocks;
+  }
+  // the passes that share a synchronise: as in expect_pauli_t (one pass needs <= 2 * 16 * 4096 doubles)
+  const size_t cap = std::min<size_t>(total, (size_t)1 << 20);
+  QCHK(ensure_partial(ket, cap));
+  std::vector<double> part(cap);
+  for (size_t p = 0; p < plan.size();) {
+    size_t used = 0, q = p;
+    for (; q < plan.size(); ++q) {
+      const size_t need = 2 * (size_t)plan[q].count * geom[q].nblocks;
+      if (used + need > cap) break;
+      const ExpectGeom& g = geom[q];
+      MelemDesc d;
+      memset(&d, 0, sizeof d);
+      d.x = terms[order[plan[q].first]].x >> g.shift;
+      d.count = plan[q].count;
+      for (uint32_t slot = 0; slot < d.count; ++slot) {
+        const PauliTerm& t = terms[order[plan[q].first + slot]];
+        if (t.ny & 1u) d.odd |= 1u << slot;
+        pauli_columns(g, ket->n, t.z, slot, d.col, &d.half);
+      }
+      const Ins ins = g.pair ? make_ins({g.hbit}, 0) : make_ins({}, 0);
+      if (d.count <= 1) melem_launch_g<T, 1>(ket, bra, g, ins, d, ket->d_partial + used);
+      else if (d.count <= 4) melem_launch_g<T, 4>(ket, bra, g, ins, d, ket->d_partial + used);
+      else melem_launch_g<T, kMelemMaxGroup>(ket, bra, g, ins, d, ket->d_partial + used);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(part.data() + used, ket->d_partial + used, need * sizeof(double), hipMemcpyDeviceToHost, ket->stream));
+      used += need;
+    }
+    HIPCHK(hipStreamSynchronize(ket->stream));
+    for (size_t at = 0; p < q; ++p) {
+      const uint32_t nb = geom[p].nblocks;
+      for (uint32_t slot = 0; slot < plan[p].count; ++slot, at += 2 * (size_t)nb) {
+        double re = 0, im = 0;
+        for (uint32_t b = 0; b < nb; ++b) re += part[at + b], im += part[at + nb + b];
+        const uint32_t id = order[plan[p].first + slot], ny = terms[id].ny;  // times i^n_Y: exact
+        values[2 * (size_t)id] = ny == 0 ? re : ny == 1 ? -im : ny == 2 ? -re : im;
+        values[2 * (size_t)id + 1] = ny == 0 ? im : ny == 1 ? re : ny == 2 ? -im : -re;
+      }
+    }
+  }
+  return QIP_OK;
+}
+
+extern "C" int qipx_state_pauli_matrix_elements(qip_hip_state* bra, qip_hip_state* ket, const uint64_t* term_start,
+                                                const uint64_t* qubits, const uint8_t* paulis, uint64_t count, double* values) try {
+  STATE_ENTER_RAW(ket);
+  QCHK(pair_meet("pauli_matrix_elements", ket, bra));
+  if (count == 0) return QIP_OK;
+  if (!values) return fail(QIP_ERR_INVALID, "pauli_matrix_elements: null result array");
+  if (count > 0xffffffffull) return fail(QIP_ERR_UNSUPPORTED, "pauli_matrix_elements: more than 2^32 - 1 terms");
+  std::vector<PauliTerm> terms;
+  QCHK(expect_reduce(ket->n, term_start, qubits, paulis, count, &terms));
+  QCHK(pair_settle(ket, bra));
+  return ket->dtype == QIP_C64 ? pauli_melem_t<double>(ket, bra, terms, values) : pauli_melem_t<float>(ket, bra, terms, values);
+} QIP_CATCH_ALL
+
 extern "C" int qip_hip_state_measure(qip_hip_state* s, const uint64_t* indices, uint32_t k,
                                      int64_t forced, double rand_u01, uint64_t* measured, double* prob) try {
   STATE_ENTER(s);

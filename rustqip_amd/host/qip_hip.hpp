@@ -409,6 +409,50 @@ template <typename P> class HipState {
     paulis.push_back(0);
     check(qipx_state_apply_pauli_rotations(h_, start.data(), qubits.data(), paulis.data(), angles.data(), terms.size()));
   }
+  /// *this <- H src, or *this + H src when `accumulate`, for H = sum_t coeffs[t] P_t (qip_hipx.h): terms as for expect_pauli,
+  /// `src` another state of the same n, precision and device (not changed).  Complete when it returns.
+  void apply_pauli_sum(HipState& src, const std::vector<std::vector<std::pair<size_t, int>>>& terms,
+                       const std::vector<std::complex<double>>& coeffs, bool accumulate = false) {
+    if (coeffs.size() != terms.size()) throw std::invalid_argument("apply_pauli_sum: one coefficient per term");
+    std::vector<uint64_t> start(1, 0), qubits;
+    std::vector<uint8_t> paulis;
+    for (const auto& term : terms) {
+      for (const auto& f : term) {
+        if (f.second < 0 || f.second > 255) throw std::invalid_argument("apply_pauli_sum: Pauli code out of range");
+        qubits.push_back(f.first);
+        paulis.push_back(uint8_t(f.second));
+      }
+      start.push_back(qubits.size());
+    }
+    qubits.push_back(0);  // (never a null data() for a list of empty terms)
+    paulis.push_back(0);
+    std::vector<double> flat(2 * coeffs.size() + 1);  // (interleaved re, im; never a null data() either)
+    for (size_t t = 0; t < coeffs.size(); ++t) flat[2 * t] = coeffs[t].real(), flat[2 * t + 1] = coeffs[t].imag();
+    check(qipx_state_apply_pauli_sum(h_, src.h_, start.data(), qubits.data(), paulis.data(), flat.data(), terms.size(), accumulate ? 1 : 0));
+  }
+  /// <*this| P |ket> of Pauli strings (qip_hipx.h): raw, in double for both precisions; an empty term gives <*this|ket>.  `ket`
+  /// may be *this.  Neither state is changed.
+  std::vector<std::complex<double>> pauli_matrix_elements(HipState& ket, const std::vector<std::vector<std::pair<size_t, int>>>& terms) {
+    std::vector<uint64_t> start(1, 0), qubits;
+    std::vector<uint8_t> paulis;
+    for (const auto& term : terms) {
+      for (const auto& f : term) {
+        if (f.second < 0 || f.second > 255) throw std::invalid_argument("pauli_matrix_elements: Pauli code out of range");
+        qubits.push_back(f.first);
+        paulis.push_back(uint8_t(f.second));
+      }
+      start.push_back(qubits.size());
+    }
+    qubits.push_back(0);  // (never a null data() for a list of empty terms)
+    paulis.push_back(0);
+    std::vector<double> flat(2 * terms.size());
+    check(qipx_state_pauli_matrix_elements(h_, ket.h_, start.data(), qubits.data(), paulis.data(), terms.size(), flat.data()));
+    std::vector<std::complex<double>> out(terms.size());
+    for (size_t t = 0; t < out.size(); ++t) out[t] = {flat[2 * t], flat[2 * t + 1]};
+    return out;
+  }
+  /// <*this|other> = sum_j conj((*this)[j]) other[j]: pauli_matrix_elements with the empty term
+  std::complex<double> inner(HipState& other) { return pauli_matrix_elements(other, {{}})[0]; }
   std::vector<double> measure_probs(const std::vector<size_t>& indices) const {
     std::vector<uint64_t> idx(indices.begin(), indices.end());
     std::vector<double> out(size_t(1) << idx.size());

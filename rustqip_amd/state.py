@@ -225,6 +225,15 @@ def pauli_rotation_passes(n: int, terms, group: int = 0) -> int:
     return int(out.value)
 
 
+def pauli_sum_passes(n: int, terms, group: int = 0) -> int:
+    """Passes HipState.apply_pauli_sum makes for `terms` on an n-qubit state when at most `group` terms of one X/Y mask share
+    a pass (0: the default of option "sum_group").  Host only: no device is needed."""
+    start, qubits, paulis, count = _pauli_terms(n, terms)
+    out = C.c_uint64()
+    _check(_ffi.lib.qipx_pauli_sum_passes(int(n), start, qubits, paulis, count, int(group), C.byref(out)))
+    return int(out.value)
+
+
 def _u64_array(values: Sequence[int]):
     arr = (C.c_uint64 * len(values))(*[int(v) for v in values])
     return arr
@@ -456,6 +465,77 @@ class HipState:
             raise CircuitError(f"{len(terms)} terms but {len(c)} coefficients")
         for _ in range(int(steps)):
             self.apply_pauli_rotations(terms, c * float(dt))
+
+    def _partner(self, other: "HipState", what: str) -> None:
+        if not isinstance(other, HipState):
+            raise CircuitError(f"{what}: the other state is not a HipState")
+        if other.n != self.n or other.dtype != self.dtype:
+            raise CircuitError(f"{what}: states differ in size or precision")
+
+    def apply_pauli_sum(self, src: "HipState", terms, coeffs, accumulate: bool = False) -> None:
+        """self <- H src, or self <- self + H src when `accumulate`, for H = sum_t coeffs[t] * terms[t] (include/qip_hipx.h):
+        real or complex coefficients, the term forms of expect_pauli.  `src` is another state of the same n, precision and
+        device and is not changed.  Terms with the same X/Y qubits share passes (at most option "sum_group" of `self` each);
+        the arithmetic is in the state's precision.  Complete when it returns."""
+        self._partner(src, "apply_pauli_sum")
+        terms = list(terms)
+        c = np.ascontiguousarray(np.asarray(coeffs, dtype=np.complex128).reshape(-1))
+        if len(c) != len(terms):
+            raise CircuitError(f"{len(terms)} terms but {len(c)} coefficients")
+        start, qubits, paulis, count = _pauli_terms(self.n, terms)
+        _check(_ffi.lib.qipx_state_apply_pauli_sum(self._h, src._h, start, qubits, paulis,
+                                                   c.view(np.float64).ctypes.data_as(C.POINTER(C.c_double)), count, int(bool(accumulate))))
+
+    def pauli_matrix_elements(self, ket: "HipState", terms) -> np.ndarray:
+        """complex128[len(terms)]: <self| P |ket> of every Pauli string in `terms` (include/qip_hipx.h), raw (divided by no
+        norm), in double for both precisions; an empty term gives <self|ket>.  `ket` may be `self`.  A value does not depend on
+        the other terms of the call.  Neither state is changed."""
+        self._partner(ket, "pauli_matrix_elements")
+        start, qubits, paulis, count = _pauli_terms(self.n, terms)
+        out = np.empty(count, dtype=np.complex128)
+        _check(_ffi.lib.qipx_state_pauli_matrix_elements(self._h, ket._h, start, qubits, paulis, count,
+                                                         out.view(np.float64).ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def inner(self, other: "HipState") -> complex:
+        """<self|other> = sum_j conj(self[j]) other[j]: pauli_matrix_elements with the empty term"""
+        return complex(self.pauli_matrix_elements(other, [{}])[0])
+
+    def adjoint_gradient(self, rot_terms, angles, obs_terms, obs_coeffs, work: "HipState") -> Tuple[float, np.ndarray]:
+        """(E, float64[T]): the energy E = <psi_T| H |psi_T> and its gradient with respect to the T angles, for
+        psi_T = R_{T-1} ... R_0 psi_0, R_k = exp(-i angles[k] * rot_terms[k]), H = sum_t obs_coeffs[t] * obs_terms[t] with real
+        coefficients.  `self` holds psi_0; `work` is a second state of the same n, precision and device whose content is
+        overwritten.
+
+        The adjoint method: the T rotations forward, lambda = H psi_T into `work`, E = Re <lambda|psi_T>, then for
+        k = T-1 .. 0: grad[k] = 2 Im <lambda| P_k |psi> (dR_k/dtheta_k = -i P_k R_k, so dE/dtheta_k = 2 Re(-i <lambda_k| P_k
+        |psi_k>)) and both states are rotated back by -angles[k] about P_k.  3T rotation passes, one Pauli sum and T + 1
+        matrix elements, against 2T runs of the ansatz with an expectation each for parameter shift.
+
+        On return `self` holds psi_0 again up to the rounding of 2T rotations (it is not restored from a copy), and `work` holds
+        H psi_T rotated back in the same way."""
+        rot_terms, obs_terms = list(rot_terms), list(obs_terms)
+        a = np.asarray(angles, dtype=np.float64).reshape(-1)
+        c = np.asarray(obs_coeffs, dtype=np.float64).reshape(-1)
+        if len(a) != len(rot_terms):
+            raise CircuitError(f"{len(rot_terms)} terms but {len(a)} angles")
+        if len(c) != len(obs_terms):
+            raise CircuitError(f"{len(obs_terms)} terms but {len(c)} coefficients")
+        if not np.all(np.isfinite(a)) or not np.all(np.isfinite(c)):
+            raise CircuitError("an angle or a coefficient is not finite")
+        self._partner(work, "adjoint_gradient")
+        if work is self or work._h.value == self._h.value:
+            raise CircuitError("adjoint_gradient: the work state is the state itself")
+        pauli_rotation_passes(self.n, rot_terms), pauli_sum_passes(self.n, obs_terms)  # (malformed terms raise here, before anything is queued)
+        self.apply_pauli_rotations(rot_terms, a)
+        work.apply_pauli_sum(self, obs_terms, c)
+        energy = work.inner(self).real
+        grad = np.zeros(len(a), dtype=np.float64)
+        for k in range(len(a) - 1, -1, -1):
+            grad[k] = 2.0 * work.pauli_matrix_elements(self, [rot_terms[k]])[0].imag
+            self.apply_pauli_rotations([rot_terms[k]], [-a[k]])
+            work.apply_pauli_rotations([rot_terms[k]], [-a[k]])
+        return float(energy), grad
 
     def measure(self, indices: Sequence[int], measured: Optional[int] = None,
                 rand_u01: float = 0.0) -> Tuple[int, float]:
