@@ -868,6 +868,31 @@ static int launch_compiled(qip_hip_state* s, const BatchRun& run, const TileSwee
   });
 }
 
+// The interpreter's lists in the wire format, packed where they are copied to the device (interpreter launches only: plans, their
+// exports, compiled segments and k_tile_gates keep TileGate<T> / TileDiagItem<T>).  A run's items may pair up (wire_pack_items), so
+// a run entry's first item and item count are rewritten against the packed list.
+template <typename T>
+static int tile_wire_pack(const std::vector<TileGate<T>>& gates, const std::vector<TileDiagItem<T>>& items, std::vector<TileWireGate<T>>* wg,
+                          std::vector<TileWireItem<T>>* wi) {
+  const TileWireOps ops = {TOP_DIAG_UNIFORM, TOP_DIAG_LANE, TOP_DIAG_LANE_CTL, TOP_DENSE0, TOP_DIAG_RUN};
+  wg->resize(gates.size());
+  wi->resize(items.size());
+  size_t n = 0;
+  for (size_t i = 0; i < gates.size(); ++i) {
+    const TileGate<T>& g = gates[i];
+    if (!wire_pack_gate<T>(g, ops, &(*wg)[i])) return fail(QIP_ERR_INVALID, "internal: a tile gate field does not fit the wire format");
+    if (g.op != TOP_DIAG_RUN) continue;
+    if ((size_t)g.nz + g.b1 > items.size()) return fail(QIP_ERR_INVALID, "internal: a diagonal run beyond the item list");
+    const long k = wire_pack_items<T>(items.data() + g.nz, g.b1, wi->data() + n);
+    if (k < 0) return fail(QIP_ERR_INVALID, "internal: a diagonal item field does not fit the wire format");
+    (*wg)[i].nz = (uint32_t)n;
+    (*wg)[i].b1 = (uint32_t)k;
+    n += (size_t)k;
+  }
+  wi->resize(n);
+  return QIP_OK;
+}
+
 template <typename T>
 static int launch_tile_segment(qip_hip_state* s, const BatchRun& run, const std::vector<const TileItem*>& seg,
                                std::vector<uint32_t> high_in, const TileStorePerm* fold = nullptr, TileSlicing* sl = nullptr,
@@ -897,17 +922,23 @@ static int launch_tile_segment(qip_hip_state* s, const BatchRun& run, const std:
   std::vector<TileGate<T>>& gates = has_runs ? interp.gates : plan.gates;
   std::vector<amp_t<T>>& mats = plan.mats;
   TilePassDesc& pd = has_runs ? interp.pd : plan.pd;
-  const size_t gates_bytes = gates.size() * sizeof(TileGate<T>);
+  // the interpreter kernel reads its lists in the wire format (qip_tile_wire.h: one 64-byte block per entry and per run item);
+  // k_tile_gates reads the gate list as it is.  Arena and pool regions start 256-byte aligned, the items at a multiple of 64.
+  const bool wire = s->tile_passes && !run.tile_jit;
+  std::vector<TileWireGate<T>> wgates;
+  std::vector<TileWireItem<T>> witems;
+  if (wire) QCHK(tile_wire_pack<T>(gates, interp.items, &wgates, &witems));
+  const size_t gates_bytes = wire ? wgates.size() * sizeof(TileWireGate<T>) : gates.size() * sizeof(TileGate<T>);
   const size_t mats_bytes = mats.size() * sizeof(amp_t<T>);
-  const size_t items_bytes = has_runs ? interp.items.size() * sizeof(TileDiagItem<T>) : 0;
-  static_assert(sizeof(TileGate<T>) % 16 == 0, "the matrix block behind the gate list stays 16-byte aligned");
-  static_assert(sizeof(amp_t<T>) * 16 % 16 == 0 && sizeof(TileDiagItem<T>) % 16 == 0, "... and the diagonal steps behind the matrices");
-  const size_t items_off = (gates_bytes + mats_bytes + 15) / 16 * 16;
-  auto upload_gates = [&]() -> int {  // after the gates are final (k_tile_passes resolves them per pass first)
+  const size_t items_bytes = has_runs ? witems.size() * sizeof(TileWireItem<T>) : 0;
+  static_assert(sizeof(TileGate<T>) % 16 == 0 && sizeof(TileWireGate<T>) % 64 == 0, "the matrix block behind the gate list stays 16-byte aligned");
+  static_assert(sizeof(amp_t<T>) * 16 % 16 == 0 && sizeof(TileWireItem<T>) == 64, "... and the diagonal steps behind the matrices, on a block boundary");
+  const size_t items_off = (gates_bytes + mats_bytes + 63) / 64 * 64;
+  auto upload_gates = [&]() -> int {
     QCHK(ensure_arena(s, items_off + items_bytes));  // one allocation: growing frees the old arena
-    QCHK(arena_upload(s, gates.data(), gates_bytes, 0));
+    QCHK(arena_upload(s, wire ? (const void*)wgates.data() : (const void*)gates.data(), gates_bytes, 0));
     if (!mats.empty()) QCHK(arena_upload(s, mats.data(), mats_bytes, gates_bytes));
-    if (items_bytes) QCHK(arena_upload(s, interp.items.data(), items_bytes, items_off));
+    if (items_bytes) QCHK(arena_upload(s, witems.data(), items_bytes, items_off));
     return QIP_OK;
   };
   TileDesc d;
@@ -960,7 +991,8 @@ static int launch_tile_segment(qip_hip_state* s, const BatchRun& run, const std:
   QCHK(upload_gates());  // descriptors up, then the timed region starts
   const TileGate<T>* dg = (const TileGate<T>*)s->arena;  // device addresses: valid only after the upload (the arena may grow / move)
   const amp_t<T>* dmats = (const amp_t<T>*)((const char*)s->arena + gates_bytes);
-  const TileDiagItem<T>* ditems = (const TileDiagItem<T>*)((const char*)s->arena + items_off);
+  const TileWireGate<T>* wg = (const TileWireGate<T>*)s->arena;
+  const TileWireItem<T>* ditems = (const TileWireItem<T>*)((const char*)s->arena + items_off);
   ProfRec rec;
   rec.cls = KC_TILE_GATES;
   if (s->profile) QCHK(prof_begin(s, KC_TILE_GATES, sweep_bytes, &rec));
@@ -969,7 +1001,7 @@ static int launch_tile_segment(qip_hip_state* s, const BatchRun& run, const std:
     return run_parts(s, run, f, &rec, [&](uint32_t k) -> int {
       Ins ins_k = ins;
       ins_k.ormask |= f.slice_or(k);
-      launch_tile_passes<T>(s->stream, grid2d(ntiles_part, 1), lds, use_nt(s), (amp_t<T>*)s->cur, ins_k, pd, dg, dmats, (amp_t<T>*)s->alt,
+      launch_tile_passes<T>(s->stream, grid2d(ntiles_part, 1), lds, use_nt(s), (amp_t<T>*)s->cur, ins_k, pd, wg, dmats, (amp_t<T>*)s->alt,
                             f.folding ? fold : nullptr, ditems);
       HIPCHK(hipGetLastError());
       return QIP_OK;

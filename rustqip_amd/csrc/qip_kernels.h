@@ -26,6 +26,10 @@ typedef __hip_internal::int32_t int32_t;
 typedef __hip_internal::int64_t int64_t;
 #endif
 
+#ifndef __HIPCC_RTC__
+#include "qip_tile_wire.h"  // the interpreter's device-side list format (k_tile_passes)
+#endif
+
 namespace qipk {
 
 constexpr int kBlock = 256;   // 4 waves of 64
@@ -1777,10 +1781,10 @@ struct TilePassDesc {
 //     loop trip instead of an inner loop (48 -> 32 at the run entry, + 4 per skipped element).  Complex<f32>: the dense 2-qubit
 //     case alone still ends in a copy of the eight amplitudes (8 v_mov_b64 in front of the latch, executed by that case only);
 //     raising the coalescer's large-interval limit halves that kernel's remaining copies but triples the unit's compile time:
-//     not taken.  Not done: ordering the
-//     dispatch so that the commonest ops (6 - 8, 27, 0, 1) resolve first; the switch is a binary compare tree of four to five
-//     scalar compare-and-branch pairs per gate, against 32 - 48 vector instructions.  tools/kernel_resources.py --isa prints the
-//     counts and the latch;
+//     not taken.  The dispatch: the wire descriptor's own code puts the commonest
+//     paths (sign-row dense, the run, the uniform and lane diagonals) at 0 .. 5, but hipcc still lowers the switch to a binary
+//     compare tree over all codes: four to five scalar compare-and-branch pairs per gate, against 32 - 48 vector instructions
+//     (an explicit first test for the low codes: not done).  tools/kernel_resources.py --isa prints the counts and the latch;
 //   * a dense gate whose second row is its first up to one sign per column (H, H.X after tile_absorb_x, Ry(pi/2)) multiplies
 //     once for both rows: (-m)*x is -(m*x) in every bit and the negation rides on the add as a source modifier, so a Hadamard is
 //     16 mul + 16 add per lane instead of 32 + 16.  The four sign patterns are four straight-line variants behind scalar branches
@@ -1910,7 +1914,8 @@ __device__ __forceinline__ void pass_dense_signs(const TileGate<T>& g, amp_t<T> 
   }
 }
 
-template <typename T, int J, int NE, bool LOOP = false>
+// SIGNS = false: the caller has routed the sign-row gates to pass_dense_signs itself (the interpreter: a dispatch code of their own)
+template <typename T, int J, int NE, bool LOOP = false, bool SIGNS = true>
 __device__ __forceinline__ void pass_dense(const TileGate<T>& g, amp_t<T> (&e)[NE], const uint32_t (&c)[NE], uint32_t cm) {
   using A = amp_t<T>;
   const bool is_x = (g.b1 & 2u) != 0, real = (g.b1 & 1u) != 0;
@@ -1931,7 +1936,7 @@ __device__ __forceinline__ void pass_dense(const TileGate<T>& g, amp_t<T> (&e)[N
     }
     return;
   }
-  if (cm == 0u && real && (g.b1 & kTileSignRows) != 0) {  // (the host sets the bit only where all four entries are non-zero)
+  if (SIGNS && cm == 0u && real && (g.b1 & kTileSignRows) != 0) {  // (the host sets the bit only where all four entries are non-zero)
     QIP_KEEP_BRANCH();
     pass_dense_signs<T, J, NE>(g, e);
   } else if (cm == 0u && g.nz == 15u) {
@@ -2101,13 +2106,49 @@ __device__ __forceinline__ void pass_dense3(const amp_t<T>* __restrict__ M, amp_
 // condition is a select (tile_sel, a factor of (1, 0)), never an `if`: a lane-dependent branch would still be compiled
 // correctly (the compiler structurizes divergent regions whatever the option says), but it brings the second register set and
 // its latch copies back for every gate.
+//
+// ONE SCALAR ROUND TRIP PER LIST ENTRY.  The lists arrive in the wire format of qip_tile_wire.h (packed by the host where the
+// lists are copied to the device): everything a code path needs before its first product — dispatch code, flags, bit indices,
+// control masks, `omask`, m[0], m[1] — is one naturally aligned 64-byte block, fetched at the loop head with ONE s_load_dwordx16
+// and waited for ONCE (wire_fetch: the empty asm that takes the sixteen words as an operand is what keeps hipcc from issuing the
+// loads field by field where each is first used: omask / wait / branch, op and masks / wait / compare tree, matrix / wait).  The
+// second row of a Complex<f64> matrix is a block of its own, read by the generic dense paths only; sign-row gates, every diagonal
+// path and the run header never touch it.  A run item is one block as well, and its element mask is resolved by the host into a
+// form code: all eight, one half by a pass bit, both halves with a factor each (an Rz on a pass bit: one item instead of two), or
+// the per-element tests for an irregular mask — a wave-uniform switch in front of straight-line products.  The products, their
+// order per amplitude and the elements they touch are those of the TileGate / TileDiagItem lists.
+#ifndef __HIPCC_RTC__  // (the interpreter is never compiled at run time; generated segments use the pass_* bodies above)
+static_assert(kTileBits == (int)kWireTileBits && kMaxIns <= (int)kWireMaxPos && kTileMaxGates == (int)kWireMaxGates,
+              "qip_tile_wire.h: the bounds its narrow fields are sized for");
+typedef uint32_t wire_words_t __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ wire_words_t wire_fetch(const void* __restrict__ p) {
+  wire_words_t w = *reinterpret_cast<const wire_words_t*>(p);
+  asm volatile("" : "+s"(w));  // all sixteen words are needed HERE: one load, one wait
+  return w;
+}
+__device__ __forceinline__ uint64_t wire_u64(uint32_t lo, uint32_t hi) { return (uint64_t)lo | ((uint64_t)hi << 32); }
+// (the word by VALUE: a bit cast applied to the vector's element itself reads the vector's first word)
+__device__ __forceinline__ float wire_f32(uint32_t u) { return __builtin_bit_cast(float, u); }
+// the amplitude whose first word is word W of a block
+template <typename T, int W> __device__ __forceinline__ amp_t<T> wire_amp(const wire_words_t& w) {
+  amp_t<T> a;
+  if constexpr (sizeof(T) == 8) {
+    a.x = __builtin_bit_cast(double, wire_u64(w[W], w[W + 1]));
+    a.y = __builtin_bit_cast(double, wire_u64(w[W + 2], w[W + 3]));
+  } else {
+    a.x = wire_f32(w[W]);
+    a.y = wire_f32(w[W + 1]);
+  }
+  return a;
+}
+
 template <typename T, bool NT, bool FOLD = false>
 __global__ __launch_bounds__(kTileBlock, 5) void k_tile_passes(amp_t<T>* __restrict__ st, Ins ins, TilePassDesc d,
-                                                                              const TileGate<T>* __restrict__ gates,
+                                                                              const TileWireGate<T>* __restrict__ gates,
                                                                               const amp_t<T>* __restrict__ mats,
                                                                               amp_t<T>* __restrict__ out = nullptr,
                                                                               TileStorePerm sp = TileStorePerm(),
-                                                                              const TileDiagItem<T>* __restrict__ diag = nullptr) {
+                                                                              const TileWireItem<T>* __restrict__ diag = nullptr) {
   using A = amp_t<T>;
   extern __shared__ __attribute__((aligned(16))) unsigned char tile_raw[];
   A* tile = reinterpret_cast<A*>(tile_raw);
@@ -2152,115 +2193,164 @@ __global__ __launch_bounds__(kTileBlock, 5) void k_tile_passes(amp_t<T>* __restr
              ((uint32_t)((i >> 2) & 1) << ps.pb[2]);
       e[i] = tile[slot_tb ^ tile_slot<A>(c[i])];
     }
-    const TileGate<T>* gp = gates + ps.first;
-    const TileGate<T>* const gend = gp + ps.count;
+    using WW = TileWireWords<T>;
+    const TileWireGate<T>* gp = gates + ps.first;
+    const TileWireGate<T>* const gend = gp + ps.count;
     for (; gp != gend; ++gp) {
-      const TileGate<T> g = *gp;  // wave-uniform (prefetching the next descriptor was measured: no gain)
-      if ((base & g.omask) != g.omask) continue;  // an outside control is 0 for this whole tile
-      const uint32_t cm_reg = g.cm_reg;
-      switch (g.op) {
-        case TOP_DIAG_RUN: {
-          const TileDiagItem<T>* ip = diag + g.nz;
-          const TileDiagItem<T>* const iend = ip + g.b1;
-// Measured on MI355X (QFT n = 30 through the interpreter, tools/build_variants.sh A/B inside one GPU call, two rounds each, ms):
-//   per-gate code paths 125.3 | runs 90.3 | + in-place products (QIP_DIAG_ASM) 85.1 | + descriptor one step ahead (QIP_DIAG_PREFETCH) 96.4
-// the prefetch costs more scalar moves than the load latency it hides (five waves per SIMD already cover it): off.
-#ifndef QIP_DIAG_PREFETCH
-#define QIP_DIAG_PREFETCH 0
-#endif
-#ifndef QIP_DIAG_ASM
-#define QIP_DIAG_ASM 1
-#endif
-#if QIP_DIAG_PREFETCH
-          TileDiagItem<T> nxt = *ip;  // wave-uniform: scalar loads, one step ahead of their use
-#endif
+      // wave-uniform.  (Fetching the NEXT descriptor ahead of its use was measured twice, here and in the run loop below: the second
+      // register set costs more scalar moves than the latency it hides.  One block, one wait removes the round trips instead.)
+      const wire_words_t w = wire_fetch(gp);
+      const uint64_t omask = wire_u64(w[kWireWOmask], w[kWireWOmask + 1]);
+      if ((base & omask) != omask) continue;  // an outside control is 0 for this whole tile
+      const uint32_t cm_reg = wire_cm_reg(w[kWireWCm]), cm_lane = wire_cm_lane(w[kWireWCm]);
+      // the gate as the pass_* bodies read it; FULL: with the second matrix row (Complex<f64>: the gate's second block)
+      auto gate_of = [&](auto full) {
+        TileGate<T> g;
+        g.b1 = w[kWireWB1];
+        g.nz = w[kWireWNz];
+        g.m[0] = wire_amp<T, WW::m0>(w);
+        g.m[1] = wire_amp<T, WW::m1>(w);
+        if constexpr (decltype(full)::v != 0) {
+          if constexpr (sizeof(T) == 8) {
+            const amp_t<T>* __restrict__ m23 = reinterpret_cast<const amp_t<T>*>(gp->m23);
+            g.m[2] = m23[0];
+            g.m[3] = m23[1];
+          } else {
+            g.m[2] = wire_amp<T, WW::m2>(w);
+            g.m[3] = wire_amp<T, WW::m3>(w);
+          }
+        }
+        return g;
+      };
+      const uint32_t code = w[kWireWCode];
+      switch (code) {
+        case WOP_SIGNS0: pass_dense_signs<T, 0, 8>(gate_of(IntC<0>()), e); break;
+        case WOP_SIGNS1: pass_dense_signs<T, 1, 8>(gate_of(IntC<0>()), e); break;
+        case WOP_SIGNS2: pass_dense_signs<T, 2, 8>(gate_of(IntC<0>()), e); break;
+        case WOP_RUN: {
+          const TileWireItem<T>* ip = diag + w[kWireWNz];
+          const TileWireItem<T>* const iend = ip + w[kWireWB1];
+          // Measured on MI355X (QFT n = 30 through the interpreter, A/B inside one GPU call, two rounds each, ms):
+          //   per-gate code paths 125.3 | runs 90.3 | + in-place products (cscale_inplace) 85.1 | + descriptor one step ahead 96.4
           for (; ip != iend;) {
-#if QIP_DIAG_PREFETCH
-            const TileDiagItem<T> it = nxt;
+            const wire_words_t it = wire_fetch(ip);
             ++ip;
-            if (ip != iend) nxt = *ip;
-#else
-            const TileDiagItem<T> it = *ip;
-            ++ip;
-#endif
-            if ((base & it.omask) != it.oval) continue;
-            A f = it.f1;
-            const uint32_t selp = it.emask_sel >> 24;
+            if ((base & wire_u64(it[WW::omask], it[WW::omask + 1])) != wire_u64(it[WW::oval], it[WW::oval + 1])) continue;
+            const uint32_t ctl = it[WW::ctl], lane = it[WW::lane];
+            const uint32_t form = wire_form(ctl);
+            A f = wire_amp<T, WW::f1>(it);
+            if (form >= WF_BOTH0) {  // two items in one: f0 on the half with pass bit J = 0, f1 on the other
+              QIP_KEEP_BRANCH();
+              A fl = wire_amp<T, WW::f0>(it);
+              if (lane != 0u) {
+                QIP_KEEP_BRANCH();
+                const bool lane_ok = (tb & wire_lane_mask(lane)) == wire_lane_val(lane);
+                fl.x = lane_ok ? fl.x : (T)1;
+                fl.y = lane_ok ? fl.y : (T)0;
+                f.x = lane_ok ? f.x : (T)1;
+                f.y = lane_ok ? f.y : (T)0;
+              }
+              if (form == WF_BOTH0) {
+                QIP_KEEP_BRANCH();
+                pass_scale<T, 0, 0, 8, true>(fl, e, c, 0u);
+                pass_scale<T, 0, 1, 8, true>(f, e, c, 0u);
+              } else if (form == WF_BOTH1) {
+                QIP_KEEP_BRANCH();
+                pass_scale<T, 1, 0, 8, true>(fl, e, c, 0u);
+                pass_scale<T, 1, 1, 8, true>(f, e, c, 0u);
+              } else {
+                QIP_KEEP_BRANCH();
+                pass_scale<T, 2, 0, 8, true>(fl, e, c, 0u);
+                pass_scale<T, 2, 1, 8, true>(f, e, c, 0u);
+              }
+              continue;
+            }
+            const uint32_t selp = wire_sel(ctl);
             if (selp != 0u) {
               QIP_KEEP_BRANCH();
-              f = tile_sel(((tb >> (selp - 1u)) & 1u) != 0u, it.f1, it.f0);
+              f = tile_sel(((tb >> (selp - 1u)) & 1u) != 0u, f, wire_amp<T, WW::f0>(it));
             }
-            if (it.lane_mask != 0u) {
+            if (lane != 0u) {
               QIP_KEEP_BRANCH();
-              const bool lane_ok = (tb & it.lane_mask) == it.lane_val;
+              const bool lane_ok = (tb & wire_lane_mask(lane)) == wire_lane_val(lane);
               f.x = lane_ok ? f.x : (T)1;
               f.y = lane_ok ? f.y : (T)0;
             }
+            switch (form) {
+              case WF_ALL: pass_scale<T, 0, -1, 8, true>(f, e, c, 0u); break;
+              case WF_LO0: pass_scale<T, 0, 0, 8, true>(f, e, c, 0u); break;
+              case WF_HI0: pass_scale<T, 0, 1, 8, true>(f, e, c, 0u); break;
+              case WF_LO1: pass_scale<T, 1, 0, 8, true>(f, e, c, 0u); break;
+              case WF_HI1: pass_scale<T, 1, 1, 8, true>(f, e, c, 0u); break;
+              case WF_LO2: pass_scale<T, 2, 0, 8, true>(f, e, c, 0u); break;
+              case WF_HI2: pass_scale<T, 2, 1, 8, true>(f, e, c, 0u); break;
+              default:  // an irregular mask: one test per element
 #pragma unroll
-            for (int i = 0; i < 8; ++i)
-              if ((it.emask_sel >> i) & 1u) {
-                QIP_KEEP_BRANCH();
-#if QIP_DIAG_ASM
-                cscale_inplace(f, e[i]);
-#else
-                e[i] = cmul(f, e[i]);
-#endif
-              }
+                for (int i = 0; i < 8; ++i)
+                  if ((ctl >> i) & 1u) {
+                    QIP_KEEP_BRANCH();
+                    cscale_inplace(f, e[i]);
+                  }
+                break;
+            }
           }
           break;
         }
-        case TOP_DIAG_UNIFORM: {
-          const A f = ((base >> g.tpos_out) & 1ull) ? g.m[1] : g.m[0];
+        case WOP_DIAG_UNIFORM: {
+          const A f = ((base >> wire_tpos_out(w[kWireWBits])) & 1ull) ? wire_amp<T, WW::m1>(w) : wire_amp<T, WW::m0>(w);
           if (f.x == (T)1 && f.y == (T)0) break;  // unit entries leave the amplitude untouched
           QIP_KEEP_BRANCH();
           pass_scale<T, 0, -1, 8, true>(f, e, c, cm_reg);
           break;
         }
-        case TOP_DIAG_LANE:
-        case TOP_DIAG_LANE_CTL: {
+        case WOP_DIAG_LANE: {  // TOP_DIAG_LANE and TOP_DIAG_LANE_CTL (the packer leaves cm_lane = 0 for the former)
           // per-lane factor: the target bit's entry (a unit entry multiplies exactly), (1, 0) where a lane-bit
           // control is 0
-          const bool outside = g.b0 == kTileOutside;
-          const bool one = outside ? ((base >> g.tpos_out) & 1ull) != 0 : ((tb >> g.b0) & 1u) != 0;
-          A f = tile_sel(one, g.m[1], g.m[0]);
-          if (g.op == TOP_DIAG_LANE_CTL) {
+          const uint32_t b0 = wire_b0(w[kWireWBits]);
+          const bool outside = b0 == kWireOutside;
+          const bool one = outside ? ((base >> wire_tpos_out(w[kWireWBits])) & 1ull) != 0 : ((tb >> b0) & 1u) != 0;
+          A f = tile_sel(one, wire_amp<T, WW::m1>(w), wire_amp<T, WW::m0>(w));
+          if (cm_lane != 0u) {
             QIP_KEEP_BRANCH();
-            const bool lane_ok = (tb & g.cm_lane) == g.cm_lane;
+            const bool lane_ok = (tb & cm_lane) == cm_lane;
             f.x = lane_ok ? f.x : (T)1;
             f.y = lane_ok ? f.y : (T)0;
           }
           pass_scale<T, 0, -1, 8, true>(f, e, c, cm_reg);
           break;
         }
-        case TOP_DIAG_REG0: pass_diag<T, 0, 8, true>(g, e, c, cm_reg, g.cm_lane != 0u, (tb & g.cm_lane) == g.cm_lane); break;
-        case TOP_DIAG_REG1: pass_diag<T, 1, 8, true>(g, e, c, cm_reg, g.cm_lane != 0u, (tb & g.cm_lane) == g.cm_lane); break;
-        case TOP_DIAG_REG2: pass_diag<T, 2, 8, true>(g, e, c, cm_reg, g.cm_lane != 0u, (tb & g.cm_lane) == g.cm_lane); break;
-        case TOP_DENSE0: pass_dense<T, 0, 8, true>(g, e, c, cm_reg); break;
-        case TOP_DENSE1: pass_dense<T, 1, 8, true>(g, e, c, cm_reg); break;
-        case TOP_DENSE2: pass_dense<T, 2, 8, true>(g, e, c, cm_reg); break;
-        case TOP_DENSE_LANE0: pass_dense_lane<T, 0>(g, e, c, cm_reg, (tb & g.cm_lane) == g.cm_lane); break;
-        case TOP_DENSE_LANE1: pass_dense_lane<T, 1>(g, e, c, cm_reg, (tb & g.cm_lane) == g.cm_lane); break;
-        case TOP_DENSE_LANE2: pass_dense_lane<T, 2>(g, e, c, cm_reg, (tb & g.cm_lane) == g.cm_lane); break;
+        // everything else keeps its TileOp value behind kWireOther
+#define QIP_WOP(op) kWireOther + (uint32_t)(op)
+        case QIP_WOP(TOP_DIAG_REG0): pass_diag<T, 0, 8, true>(gate_of(IntC<0>()), e, c, cm_reg, cm_lane != 0u, (tb & cm_lane) == cm_lane); break;
+        case QIP_WOP(TOP_DIAG_REG1): pass_diag<T, 1, 8, true>(gate_of(IntC<0>()), e, c, cm_reg, cm_lane != 0u, (tb & cm_lane) == cm_lane); break;
+        case QIP_WOP(TOP_DIAG_REG2): pass_diag<T, 2, 8, true>(gate_of(IntC<0>()), e, c, cm_reg, cm_lane != 0u, (tb & cm_lane) == cm_lane); break;
+        case QIP_WOP(TOP_DENSE0): pass_dense<T, 0, 8, true, false>(gate_of(IntC<1>()), e, c, cm_reg); break;
+        case QIP_WOP(TOP_DENSE1): pass_dense<T, 1, 8, true, false>(gate_of(IntC<1>()), e, c, cm_reg); break;
+        case QIP_WOP(TOP_DENSE2): pass_dense<T, 2, 8, true, false>(gate_of(IntC<1>()), e, c, cm_reg); break;
+        case QIP_WOP(TOP_DENSE_LANE0): pass_dense_lane<T, 0>(gate_of(IntC<1>()), e, c, cm_reg, (tb & cm_lane) == cm_lane); break;
+        case QIP_WOP(TOP_DENSE_LANE1): pass_dense_lane<T, 1>(gate_of(IntC<1>()), e, c, cm_reg, (tb & cm_lane) == cm_lane); break;
+        case QIP_WOP(TOP_DENSE_LANE2): pass_dense_lane<T, 2>(gate_of(IntC<1>()), e, c, cm_reg, (tb & cm_lane) == cm_lane); break;
 #define QIP_D2Q(JA, JB) \
-  pass_dense2<T, JA, JB>(mats + 16u * g.nz, e, c, cm_reg, g.cm_lane != 0u, (tb & g.cm_lane) == g.cm_lane)
-        case TOP_DENSE2Q_01: QIP_D2Q(0, 1); break;
-        case TOP_DENSE2Q_02: QIP_D2Q(0, 2); break;
-        case TOP_DENSE2Q_10: QIP_D2Q(1, 0); break;
-        case TOP_DENSE2Q_12: QIP_D2Q(1, 2); break;
-        case TOP_DENSE2Q_20: QIP_D2Q(2, 0); break;
-        case TOP_DENSE2Q_21: QIP_D2Q(2, 1); break;
+  pass_dense2<T, JA, JB>(mats + 16u * w[kWireWNz], e, c, cm_reg, cm_lane != 0u, (tb & cm_lane) == cm_lane)
+        case QIP_WOP(TOP_DENSE2Q_01): QIP_D2Q(0, 1); break;
+        case QIP_WOP(TOP_DENSE2Q_02): QIP_D2Q(0, 2); break;
+        case QIP_WOP(TOP_DENSE2Q_10): QIP_D2Q(1, 0); break;
+        case QIP_WOP(TOP_DENSE2Q_12): QIP_D2Q(1, 2); break;
+        case QIP_WOP(TOP_DENSE2Q_20): QIP_D2Q(2, 0); break;
+        case QIP_WOP(TOP_DENSE2Q_21): QIP_D2Q(2, 1); break;
 #undef QIP_D2Q
-        case TOP_SWAP_01: pass_swap<T, 0, 1, 8, true>(e, c, cm_reg, g.cm_lane != 0u, (tb & g.cm_lane) == g.cm_lane); break;
-        case TOP_SWAP_02: pass_swap<T, 0, 2, 8, true>(e, c, cm_reg, g.cm_lane != 0u, (tb & g.cm_lane) == g.cm_lane); break;
-        case TOP_SWAP_12: pass_swap<T, 1, 2, 8, true>(e, c, cm_reg, g.cm_lane != 0u, (tb & g.cm_lane) == g.cm_lane); break;
-#define QIP_D3Q(JA, JB, JC) pass_dense3<T, JA, JB, JC>(mats + 16u * g.nz, e, g.cm_lane != 0u, (tb & g.cm_lane) == g.cm_lane)
-        case TOP_DENSE3Q_012: QIP_D3Q(0, 1, 2); break;
-        case TOP_DENSE3Q_021: QIP_D3Q(0, 2, 1); break;
-        case TOP_DENSE3Q_102: QIP_D3Q(1, 0, 2); break;
-        case TOP_DENSE3Q_120: QIP_D3Q(1, 2, 0); break;
-        case TOP_DENSE3Q_201: QIP_D3Q(2, 0, 1); break;
-        case TOP_DENSE3Q_210: QIP_D3Q(2, 1, 0); break;
+        case QIP_WOP(TOP_SWAP_01): pass_swap<T, 0, 1, 8, true>(e, c, cm_reg, cm_lane != 0u, (tb & cm_lane) == cm_lane); break;
+        case QIP_WOP(TOP_SWAP_02): pass_swap<T, 0, 2, 8, true>(e, c, cm_reg, cm_lane != 0u, (tb & cm_lane) == cm_lane); break;
+        case QIP_WOP(TOP_SWAP_12): pass_swap<T, 1, 2, 8, true>(e, c, cm_reg, cm_lane != 0u, (tb & cm_lane) == cm_lane); break;
+#define QIP_D3Q(JA, JB, JC) pass_dense3<T, JA, JB, JC>(mats + 16u * w[kWireWNz], e, cm_lane != 0u, (tb & cm_lane) == cm_lane)
+        case QIP_WOP(TOP_DENSE3Q_012): QIP_D3Q(0, 1, 2); break;
+        case QIP_WOP(TOP_DENSE3Q_021): QIP_D3Q(0, 2, 1); break;
+        case QIP_WOP(TOP_DENSE3Q_102): QIP_D3Q(1, 0, 2); break;
+        case QIP_WOP(TOP_DENSE3Q_120): QIP_D3Q(1, 2, 0); break;
+        case QIP_WOP(TOP_DENSE3Q_201): QIP_D3Q(2, 0, 1); break;
+        case QIP_WOP(TOP_DENSE3Q_210): QIP_D3Q(2, 1, 0); break;
 #undef QIP_D3Q
+#undef QIP_WOP
         default: break;
       }
     }
@@ -2279,6 +2369,7 @@ __global__ __launch_bounds__(kTileBlock, 5) void k_tile_passes(amp_t<T>* __restr
     }
   }
 }
+#endif  // !__HIPCC_RTC__
 
 // ---- dense 4- / 5-qubit gate on the matrix cores through an LDS-resident tile ----------------------------------------------
 // k_gate_kq_mfma reads its operands where they lie: 16 groups x 4 sub-indices per load instruction = four 256-B runs, 65 %

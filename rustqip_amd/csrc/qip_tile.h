@@ -117,8 +117,8 @@ extern int64_t g_tile_diag_runs;  // global option "tile_diag_runs" (1 = on)
 // qip_tile_interp.hip: one k_tile_passes launch (`fold` non-null: the sweep stores packed into `out`); errors via hipGetLastError
 template <typename T>
 void launch_tile_passes(hipStream_t stream, dim3 grid, size_t lds, bool nt, amp_t<T>* st, const Ins& ins, const TilePassDesc& pd,
-                        const TileGate<T>* gates, const amp_t<T>* mats, amp_t<T>* out, const TileStorePerm* fold,
-                        const TileDiagItem<T>* items);
+                        const TileWireGate<T>* gates, const amp_t<T>* mats, amp_t<T>* out, const TileStorePerm* fold,
+                        const TileWireItem<T>* items);
 
 // A segment's item list with its uncontrolled X gates absorbed (INTERPRETER launches only, like the diagonal runs: plans, the
 // generators, the one-op sweeps and the wide path never see it).  Every X target of a segment is a tile position, so X is a fixed

@@ -11,8 +11,8 @@
 
 template <typename T>
 void launch_tile_passes(hipStream_t stream, dim3 grid, size_t lds, bool nt, amp_t<T>* st, const Ins& ins, const TilePassDesc& pd,
-                        const TileGate<T>* gates, const amp_t<T>* mats, amp_t<T>* out, const TileStorePerm* fold,
-                        const TileDiagItem<T>* items) {
+                        const TileWireGate<T>* gates, const amp_t<T>* mats, amp_t<T>* out, const TileStorePerm* fold,
+                        const TileWireItem<T>* items) {
   if (fold) {
 #define TPF(NTV) hipLaunchKernelGGL((k_tile_passes<T, NTV, true>), grid, dim3(kTileBlock), lds, stream, st, ins, pd, gates, mats, out, *fold, items)
     if (nt) TPF(true);
@@ -25,7 +25,7 @@ void launch_tile_passes(hipStream_t stream, dim3 grid, size_t lds, bool nt, amp_
 #undef TP
   }
 }
-template void launch_tile_passes<double>(hipStream_t, dim3, size_t, bool, amp_t<double>*, const Ins&, const TilePassDesc&, const TileGate<double>*,
-                                         const amp_t<double>*, amp_t<double>*, const TileStorePerm*, const TileDiagItem<double>*);
-template void launch_tile_passes<float>(hipStream_t, dim3, size_t, bool, amp_t<float>*, const Ins&, const TilePassDesc&, const TileGate<float>*,
-                                        const amp_t<float>*, amp_t<float>*, const TileStorePerm*, const TileDiagItem<float>*);
+template void launch_tile_passes<double>(hipStream_t, dim3, size_t, bool, amp_t<double>*, const Ins&, const TilePassDesc&, const TileWireGate<double>*,
+                                         const amp_t<double>*, amp_t<double>*, const TileStorePerm*, const TileWireItem<double>*);
+template void launch_tile_passes<float>(hipStream_t, dim3, size_t, bool, amp_t<float>*, const Ins&, const TilePassDesc&, const TileWireGate<float>*,
+                                        const amp_t<float>*, amp_t<float>*, const TileStorePerm*, const TileWireItem<float>*);

@@ -40,7 +40,7 @@ def demangle(names):
 CLASSES = (("mul64", r"v_mul_f64"), ("add64", r"v_add_f64"), ("mul32", r"v_mul_f32"), ("add32", r"v_(add|sub|subrev)_f32"),
            ("mov", r"v_mov_b(64|32)"), ("cnd", r"v_cndmask"), ("ds", r"ds_"), ("sload", r"s_(buffer_)?load"),
            ("branch", r"s_c?branch"))
-GATE_BYTES = (0x70, 0x50)  # sizeof(TileGate<double>), sizeof(TileGate<float>)
+GATE_BYTES = (0x80, 0x40)  # sizeof(TileWireGate<double>), sizeof(TileWireGate<float>): what the interpreter's gate loop advances by
 
 
 def count(lines):
@@ -86,7 +86,7 @@ def functions(path):
 def latch(blocks):
     """indices of the blocks that fall through into the pointer advance, and of that block"""
     for i, (_, ins) in enumerate(blocks):
-        if any(re.match(r"s_add_u32 (s\d+), \1, 0x%x$" % b, x) for x in ins for b in GATE_BYTES):
+        if any(re.match(r"s_add_u32 (s\d+), \1, (0x%x|%d)$" % (b, b), x) for x in ins for b in GATE_BYTES):  # (the assembler prints 64 in decimal)
             j = i
             while j > 0 and blocks[j - 1][1] and not re.match(r"s_branch|s_endpgm|s_setpc", blocks[j - 1][1][-1]) and \
                     all(re.match(r"v_mov|v_accvgpr", x) for x in blocks[j - 1][1]):
