@@ -220,6 +220,15 @@ impl<P: HipPrecision> HipState<P> {
     pub fn inner(&mut self, other: &mut HipState<P>) -> Result<(f64, f64), HipError> {
         Ok(self.pauli_matrix_elements(other, &[Vec::new()])?[0])
     }
+    /// The raw reduced density matrix of up to six qubits (`include/qip_hipx.h`): `2^k` rows of `2^k` entries `(re, im)`,
+    /// `rho[a][a'] = sum_b psi[a,b] conj(psi[a',b])`, bit `i` of `a` = qubit `indices[i]`; not divided by the norm.  The lower
+    /// triangle is the exact conjugate of the upper.  The state is not changed.
+    pub fn reduced_density_matrix(&mut self, indices: &[u64]) -> Result<Vec<Vec<(f64, f64)>>, HipError> {
+        let m = 1usize << indices.len().min(6);
+        let mut flat = vec![0f64; 2 * m * m];
+        check(unsafe { sys_ext::qipx_state_reduced_density(self.h, indices.as_ptr(), indices.len() as u32, flat.as_mut_ptr()) })?;
+        Ok(flat.chunks(2 * m).map(|row| row.chunks(2).map(|c| (c[0], c[1])).collect()).collect())
+    }
     pub fn raw(&mut self) -> *mut sys::qip_hip_state {
         self.h
     }

@@ -91,4 +91,7 @@ extern "C" {
         count: u64,
         values: *mut c_double,
     ) -> c_int;
+    /// rho[2 (a M + a')] + i rho[.. + 1] = sum_b psi[a,b] conj(psi[a',b]), M = 2^k, 1 <= k <= 6: the raw reduced density matrix of
+    /// the qubits `indices` (bit i of a = qubit indices[i]), in double for both precisions.  The state is not changed.
+    pub fn qipx_state_reduced_density(s: *mut qip_hip_state, indices: *const u64, k: u32, rho: *mut c_double) -> c_int;
 }

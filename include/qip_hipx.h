@@ -198,6 +198,57 @@ int qipx_pauli_sum_passes(uint32_t n, const uint64_t* term_start, const uint64_t
 int qipx_state_pauli_matrix_elements(qip_hip_state* bra, qip_hip_state* ket, const uint64_t* term_start, const uint64_t* qubits,
                                      const uint8_t* paulis, uint64_t count, double* values);
 
+/* The reduced density matrix of up to six qubits.  (Purely additive again.)
+ *
+ * With the amplitudes seen as a 2^k x 2^(n-k) matrix Psi (row a = the bits of the k qubits, column b = all other bits),
+ *   rho[a][a'] = sum_b psi[a,b] * conj(psi[a',b]),       rho = Psi Psi^H = Tr_rest |psi><psi|.
+ * `rho` holds 2 * 4^k doubles, row-major with M = 2^k: rho[2 (a M + a')] and rho[2 (a M + a') + 1] are the real and imaginary part
+ * of rho[a][a'].  Bit i of a and of a' is the bit of qubit indices[i], the outcome convention of qip_hip_state_measure_probs; qubit
+ * q is index bit n-1-q.  The value is raw: it is NOT divided by the norm, so tr rho = sum |psi_j|^2 and the diagonal is what
+ * measure_probs returns (to the rounding of the products on a Complex<f32> state, see below).
+ *
+ * Supported: 1 <= k <= 6, k = n included (one column: rho = psi psi^H).  k > 6 is QIP_ERR_UNSUPPORTED with a message that names
+ * k.  The index list is checked as by the measurement calls, with their messages (k = 0, an index >= n, a repeated index:
+ * QIP_ERR_INVALID).  A null `rho` and a null handle are QIP_ERR_INVALID: there is no host fall-back.  Everything is checked
+ * before the first launch.
+ *
+ * Precision.  Products and sums are formed in double for Complex<f64> and Complex<f32> states alike; f32 amplitudes are widened
+ * before the first product, as in qipx_state_expect_pauli.
+ *
+ * Arithmetic.  Re rho[a][a'] = sum_b (xr xr' + xi xi'), Im rho[a][a'] = sum_b (xi xr' - xr xi') with psi[a,b] = xr + i xi and
+ * psi[a',b] = xr' + i xi'.  k <= 3: fused multiply-adds into one running sum per entry and lane.  k = 4 .. 6: the f64 matrix
+ * instruction v_mfma_f64_16x16x4_f64 on 16 x 16 blocks I <= J of rho, four columns b per step; on a diagonal block the imaginary
+ * part is T - T^T for the accumulated T = Xi Xr^T.
+ *
+ * Exact structure.  The library computes the entries a <= a' (in the sorted order below) once and mirrors them: rho[a'][a] is bit
+ * for bit the conjugate of rho[a][a'], and every diagonal imaginary part is +0.0.
+ *
+ * Determinism.  No atomics.  Every block writes one partial matrix to the handle's reduction scratch; a second kernel adds the
+ * partial matrices entry by entry in block order on the device, so that only 4^k entries cross PCIe.  The same call on the same
+ * state returns the same bits.  The kernels work on the qubits' index positions in ascending order and the host permutes rows
+ * and columns: the result for a permuted index list is the bit-exact row/column permutation of the result for the sorted list.
+ *
+ * Scratch.  k <= 3: at most 4096 blocks of 4^k doubles (2 MiB).  k = 4 .. 6: at most 1024 blocks of 512 / 1536 / 5120 doubles (the
+ * blocks I <= J only): 4 / 12 / 40 MiB, plus one matrix for the fold.  It is the handle's reduction scratch, grown on demand and
+ * freed with the handle.
+ *
+ * Error statement.  Let S = sum_b |psi[a,b]| |psi[a',b]| <= sqrt(rho[a][a] rho[a'][a']) (Cauchy-Schwarz) and u = 2^-53.  To first
+ * order an entry is within c u * 2 S of the exact sum over the stored amplitudes (each part of an entry adds two products per
+ * column), c the longest chain of additions a product passes through:
+ *   k <= 3    lane chain: 2^(n-k-20) groups for n - k >= 20 (4096 blocks of 256 lanes; at most 512 at n = 30), two fused
+ *             multiply-adds each; wave tree 6; the block's four waves 3; block fold 4096 / 64 = 64 in a lane, then a tree of 6;
+ *             c <= 2 * 512 + 6 + 3 + 64 + 6 = 1103 at n = 30, k = 1.
+ *   k >= 4    a wave's accumulators are added to a second set and cleared every 32 steps of four columns: inner chain 32 * 4 = 128
+ *             columns; outer chain: a wave meets 2^(n-k) / 4096 columns (1024 blocks, 4 waves to a set of block pairs; 2 at k = 6),
+ *             2^14 at n = 30, k = 4, that is 128 additions; the block's waves 3; block fold 1024 / 64 = 16, then a tree of 6;
+ *             T - T^T one more; c <= 2 * 128 + 128 + 3 + 16 + 6 + 1 = 410 at n = 30, k = 4.
+ * Both stay below 1e-12 S / (2 S u) = 4500: the result is within 1e-12 * sqrt(rho[a][a] rho[a'][a']) of the exact value for every
+ * n <= 30 (tests/test_gpu_f2_reduced_density.py holds every entry to that bar).
+ *
+ * Calling contract.  The state is not changed.  A relabelled state (option "tile_relabel" = 3) is put back in the caller's order on
+ * entry, as by the measurement calls.  The call is ordered after the work queued on the handle and complete when it returns. */
+int qipx_state_reduced_density(qip_hip_state* s, const uint64_t* indices, uint32_t k, double* rho);
+
 #ifdef __cplusplus
 }
 #endif

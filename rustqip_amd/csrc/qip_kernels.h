@@ -3962,4 +3962,311 @@ __global__ __launch_bounds__(kBlock) void k_collapse(amp_t<T>* __restrict__ st, 
   }
 }
 
+
+// ---- reduced density matrices (qipx_state_reduced_density, include/qip_hipx.h) -------------------------------------------
+// rho[a][a'] = sum_b psi[a,b] conj(psi[a',b]) over the k SORTED positions (bit j of a = the j-th lowest position); only a <= a' is
+// formed: Re = sum xr xr' + xi xi', Im = sum xi xr' - xr xi', every product and sum in double (f32 amplitudes widened first),
+// fused multiply-adds written out (the build has -ffp-contract=off).  No atomics: one partial matrix per block in block order.
+//
+// k = 1 .. 3 — register accumulators.  All positions in units of ELEMENTS (E = f32x4: two amplitudes, the half bit apart):
+//   high   KH positions >= 6, opened by `ins`: a lane walks their 2^KH values with one load each — every load instruction of a
+//          wave is one contiguous 1-KiB row (the four waves of a block take neighbouring rows);
+//   low    KL positions < 6 = lane-id bits.  The lane loads U = 2^KL rows and the wave transposes: at stage i the lanes that
+//          differ in lane bit lpos[i] swap the halves of their row set (select + shfl_xor, as k_gate1q's partner exchange), after
+//          which array index bit i IS index bit lpos[i] — every lane then owns whole groups, whichever rows they came from;
+//   B0     index bit 0 (the half of a packed element) is the lowest position: the halves are matrix rows 2e and 2e + 1;
+//          otherwise the halves of a packed element are two columns b.
+// Accumulator slots: M diagonal sums, then (re, im) of the pairs a < a' in row-major order: M^2 doubles, 64 at k = 3.
+struct DensDesc {
+  uint32_t lpos[6];  // the low positions, ascending
+  uint64_t coff[8];  // element offset of the c-th value of the high positions
+  uint64_t nrows;    // rows of 64 work items
+  uint32_t nlane;    // work items of a row (64; fewer when the whole state is smaller)
+};
+
+template <typename T, int KE, int KL, bool B0, typename E = amp_t<T>>
+__global__ __launch_bounds__(kBlock) void k_density_small(const E* __restrict__ st, Ins ins, DensDesc d,
+                                                          double* __restrict__ partial) {
+  constexpr bool PACKED = !SameT<E, amp_t<T>>::v;
+  static_assert(PACKED || !B0, "the half bit exists in packed elements only");
+  constexpr int KH = KE - KL, ME = 1 << KE, NC = 1 << KH, U = 1 << KL, R = ME >= 4 ? 1 : 4 / ME;
+  constexpr int M = B0 ? 2 * ME : ME, NCOL = (PACKED && !B0) ? 2 : 1, NP = M * (M - 1) / 2, NACC = M * M;
+  __shared__ double smem[(kBlock / 64) * NACC];
+  double dg[M], re[NP], im[NP];
+#pragma unroll
+  for (int a = 0; a < M; ++a) dg[a] = 0.0;
+#pragma unroll
+  for (int p = 0; p < NP; ++p) re[p] = im[p] = 0.0;
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint64_t nwaves = (uint64_t)gridDim.x * (kBlock / 64);
+  for (uint64_t row0 = ((uint64_t)blockIdx.x * (kBlock / 64) + wv) * (U * R); row0 < d.nrows; row0 += nwaves * (U * R)) {
+    E x[R][U][NC];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const uint64_t row = row0 + (uint64_t)(r * U + u);
+        const bool valid = row < d.nrows && lane < d.nlane;
+        const uint64_t base = insert_bits<KH>((row << 6) | lane, ins);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          E e = {};
+          if (valid) e = __builtin_nontemporal_load(st + (base | d.coff[c]));
+          x[r][u][c] = e;
+        }
+      }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+#pragma unroll
+      for (int i = 0; i < KL; ++i) {
+        const bool up = (lane >> d.lpos[i]) & 1u;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          if ((u >> i) & 1) continue;
+          const int u1 = u | (1 << i);
+#pragma unroll
+          for (int c = 0; c < NC; ++c) {
+            const E e0 = x[r][u][c], e1 = x[r][u1][c];
+            const E got = shfl_xor_e<E>(up ? e0 : e1, 1 << d.lpos[i]);
+            x[r][u][c] = up ? got : e0;
+            x[r][u1][c] = up ? e1 : got;
+          }
+        }
+      }
+#pragma unroll
+      for (int col = 0; col < NCOL; ++col) {
+        double vr[M], vi[M];
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+#pragma unroll
+          for (int u = 0; u < U; ++u) {
+            const E e = x[r][u][c];
+            const int ie = (c << KL) | u;
+            if constexpr (!PACKED) {
+              vr[ie] = (double)e.x;
+              vi[ie] = (double)e.y;
+            } else if constexpr (B0) {
+              vr[2 * ie] = (double)e.x;
+              vi[2 * ie] = (double)e.y;
+              vr[2 * ie + 1] = (double)e.z;
+              vi[2 * ie + 1] = (double)e.w;
+            } else {
+              vr[ie] = (double)(col ? e.z : e.x);
+              vi[ie] = (double)(col ? e.w : e.y);
+            }
+          }
+#pragma unroll
+        for (int a = 0; a < M; ++a) dg[a] = __builtin_fma(vi[a], vi[a], __builtin_fma(vr[a], vr[a], dg[a]));
+        int p = 0;
+#pragma unroll
+        for (int a = 0; a < M; ++a)
+#pragma unroll
+          for (int a2 = a + 1; a2 < M; ++a2, ++p) {
+            re[p] = __builtin_fma(vi[a], vi[a2], __builtin_fma(vr[a], vr[a2], re[p]));
+            im[p] = __builtin_fma(-vr[a], vi[a2], __builtin_fma(vi[a], vr[a2], im[p]));
+          }
+      }
+    }
+  }
+  // the wave (shuffle tree), then the block's four waves in wave order
+  auto fold = [&](double v, int slot) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if (lane == 0) smem[wv * NACC + slot] = v;
+  };
+#pragma unroll
+  for (int a = 0; a < M; ++a) fold(dg[a], a);
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    fold(re[p], M + 2 * p);
+    fold(im[p], M + 2 * p + 1);
+  }
+  __syncthreads();
+  for (int slot = threadIdx.x; slot < NACC; slot += kBlock)
+    partial[(uint64_t)blockIdx.x * NACC + slot] = ((smem[slot] + smem[NACC + slot]) + smem[2 * NACC + slot]) + smem[3 * NACC + slot];
+}
+
+// k = 4 .. 6 — f64 matrix cores.  With Psi a 2^k x (columns) matrix, rho = Psi Psi^H is a Hermitian rank update.  The operand
+// layouts of v_mfma_f64_16x16x4_f64 are A[lane & 15][lane >> 4] and B[lane >> 4][lane & 15]: ONE register holding
+// X[row = lane & 15][column = lane >> 4] of a 16-row block of Psi is the A operand X and the B operand X^T at once, so Xr and Xi
+// (real and imaginary parts of four columns) feed both sides with no transposition.  Per four columns and row blocks I <= J
+//   Re rho_IJ += Xr_I Xr_J^T + Xi_I Xi_J^T,     Im rho_IJ += Xi_I Xr_J^T - Xr_I Xi_J^T    (the negated operand is exact);
+// for I = J the second accumulator holds T = Xi Xr^T and the host forms Im = T - T^T: 3 / 10 / 36 instructions for k = 4 / 5 / 6.
+// C/D layout of the f64 form: column = lane & 15, row = (lane >> 4) + 4 * reg.
+//
+// A block stages one tile at a time in LDS with 16-byte loads in contiguous runs of 2^L elements: the tile is (the 2^kh values of
+// the positions >= L) x (one run); a lane's loads of the next tile are in flight while the block works on this one.  A wave owns
+// a whole rho (at k = 6 half of its block pairs); the waves that own the same pairs share a tile's columns four at a time and
+// read their operands from LDS by amplitude index: rowoff (the position bits of the lane's rows, swizzled) ^ coltab[column].
+// Columns past the end (fewer than four in the whole state) are zeros.  Every kDensFlush steps the accumulators are added to a
+// second set and cleared, which keeps every accumulation chain short (the error statement of include/qip_hipx.h).  At the end
+// the matrices of the waves that share block pairs are added in wave order through LDS:
+// partial[block * nout + (part * NPAIR + pair) * 256 + reg * 64 + lane].
+struct DensTileDesc {
+  uint64_t hoff[64];  // element offset of the values of the positions >= L
+  uint64_t ntiles;
+  uint32_t L, kh;     // log2 elements of a run; positions >= L
+  uint32_t la;        // log2 AMPLITUDES of a run (L + 1 for packed elements)
+  uint32_t rowmask;   // the positions inside a run, as amplitude-index bits (the half bit included when it is a position)
+  uint32_t kla;       // popcount(rowmask)
+  uint32_t lcols;     // log2 columns of a tile = la - kla
+  // LDS swizzle, in 16-byte slots: slot s of the tile is kept at s ^ (sum over j of bit sw_src[j] of s, moved to bit sw_dst[j]).
+  // The 16 lanes of an operand read differ in the four lowest row bits; those that are not among slot bits 0..3 already are
+  // folded into the free ones of these, so the 16 reads of 16 bytes fall into 16 different bank groups (a row stride of 512 B or more
+  // would otherwise put all of them into one).  sw_dst < 4 <= sw_src: writes of 16 consecutive slots stay consecutive.
+  uint32_t nsw, sw_src[4], sw_dst[4];  // nsw pairs in use; the others read bit 31, which no slot has
+};
+constexpr int kDensTileBytes = 32768;
+constexpr int kDensFlush = 32;
+
+__device__ __forceinline__ uint32_t deposit_bits(uint32_t v, uint32_t mask) {
+  uint32_t r = 0;
+  for (uint32_t b = 0; mask; mask &= mask - 1u, ++b) r |= ((v >> b) & 1u) << (__ffs((int)mask) - 1);
+  return r;
+}
+
+template <typename T, int K, typename E = amp_t<T>>
+__global__ __launch_bounds__(kBlock) void k_density_mfma(const E* __restrict__ st, Ins ins, DensTileDesc d, uint64_t nout,
+                                                         double* __restrict__ partial) {
+  constexpr int M = 1 << K, NB = M / 16, NPAIR = NB * (NB + 1) / 2;
+  constexpr bool SPLIT = K < 5;  // three instructions per step: the two products of Re keep accumulators of their own
+  static_assert(NPAIR * 256 * sizeof(double) <= kDensTileBytes, "the wave fold reuses the tile");
+  __shared__ __attribute__((aligned(16))) unsigned char lds[kDensTileBytes];
+  __shared__ uint64_t hofft[64];
+  __shared__ unsigned short coltab[512];  // (no uint16_t under hiprtc)
+  E* tile = reinterpret_cast<E*>(lds);
+  const amp_t<T>* tamp = reinterpret_cast<const amp_t<T>*>(lds);
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6, r = lane & 15u, c = lane >> 4;
+  const uint32_t ncols = 1u << d.lcols, nsteps = ncols >= 4u ? ncols / 4u : 1u;
+  const uint32_t colmask = ((1u << d.la) - 1u) & ~d.rowmask;
+  constexpr uint32_t kSlotShift = sizeof(amp_t<T>) == 16 ? 0u : 1u;  // amplitudes per 16-byte slot, log2
+  auto swz = [&](uint32_t slot) {  // (unused pairs read bit 31, which no slot has)
+    uint32_t x = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) x |= ((slot >> d.sw_src[j]) & 1u) << d.sw_dst[j];
+    return x;
+  };
+  if (threadIdx.x < 64) hofft[threadIdx.x] = threadIdx.x < (1u << d.kh) ? d.hoff[threadIdx.x] : 0ull;
+  for (uint32_t i = threadIdx.x; i < ncols; i += kBlock) coltab[i] = (unsigned short)deposit_bits(i, colmask);
+  uint32_t rowoff[NB];
+#pragma unroll
+  for (int I = 0; I < NB; ++I) {
+    const uint32_t a = 16u * I + r;
+    const uint32_t at = ((a >> d.kla) << d.la) | deposit_bits(a & ((1u << d.kla) - 1u), d.rowmask);
+    rowoff[I] = at ^ (swz(at >> kSlotShift) << kSlotShift);  // (the swizzle reads row bits only: a column adds nothing to it)
+  }
+  // K = 6: the ten block pairs take 80 accumulators, twice that with the second set, so the waves of a block form two groups
+  // of two: group 0 owns pairs 0..4 = (0,0) (0,1) (0,2) (0,3) (1,1), group 1 pairs 5..9 = (1,2) (1,3) (2,2) (2,3) (3,3), 18
+  // instructions per step each, and the two waves of a group share the tile's columns.  K = 4, 5: one group of four waves.
+  constexpr int NG = K == 6 ? 2 : 1, WG = (kBlock / 64) / NG, NPW = NPAIR / NG;
+  static_assert(NPW * NG == NPAIR, "the pairs split evenly");
+  const uint32_t grp = wv / WG, wi = wv % WG;
+  const v4f64 zero4 = {0.0, 0.0, 0.0, 0.0};
+  v4f64 are[NPW], aim[NPW], are2[SPLIT ? NPW : 1], tre[NPW], tim[NPW];
+#pragma unroll
+  for (int p = 0; p < NPW; ++p) are[p] = aim[p] = tre[p] = tim[p] = zero4;
+#pragma unroll
+  for (int p = 0; p < (SPLIT ? NPW : 1); ++p) are2[p] = zero4;
+  auto flush = [&]() {
+#pragma unroll
+    for (int p = 0; p < NPW; ++p) {
+      if constexpr (SPLIT) {
+        tre[p] += are[p] + are2[p];
+        are2[p] = zero4;
+      } else {
+        tre[p] += are[p];
+      }
+      tim[p] += aim[p];
+      are[p] = aim[p] = zero4;
+    }
+  };
+  const uint32_t tile_elems = 1u << (d.L + d.kh), runmask = (1u << d.L) - 1u;
+  // a lane's share of a tile, all of its loads in flight at once, fetched into registers while the block works on the tile before
+  constexpr int kPerLane = kDensTileBytes / 16 / kBlock;
+  E held[kPerLane];
+  auto fetch = [&](uint64_t t) {
+    const uint64_t base = insert_bits<-1>(t << d.L, ins);
+#pragma unroll
+    for (int i = 0; i < kPerLane; ++i) {
+      const uint32_t e = threadIdx.x + (uint32_t)i * kBlock;
+      if (e < tile_elems) held[i] = __builtin_nontemporal_load(st + (base | hofft[e >> d.L] | (uint64_t)(e & runmask)));
+    }
+  };
+  uint32_t pending = 0;
+  // the steps of one tile for the wave's group G: pairs G * NPW .. in row-major order of (I <= J)
+  auto steps = [&](auto gc) {
+    constexpr int G = decltype(gc)::v;
+    for (uint32_t s = wi; s < nsteps; s += WG) {
+      const uint32_t col = 4u * s + c;
+      const bool live = col < ncols;
+      const uint32_t coff = coltab[live ? col : 0u];
+      double xr[NB], xi[NB];
+#pragma unroll
+      for (int I = 0; I < NB; ++I) {
+        const amp_t<T> v = tamp[rowoff[I] ^ coff];
+        xr[I] = live ? (double)v.x : 0.0;
+        xi[I] = live ? (double)v.y : 0.0;
+      }
+      int p = 0;
+#pragma unroll
+      for (int I = 0; I < NB; ++I)
+#pragma unroll
+        for (int J = I; J < NB; ++J, ++p)
+          if (p >= G * NPW && p < (G + 1) * NPW) {
+            are[p - G * NPW] = mfma16(xr[I], xr[J], are[p - G * NPW]);
+            aim[p - G * NPW] = mfma16(xi[I], xr[J], aim[p - G * NPW]);
+          }
+      p = 0;
+#pragma unroll
+      for (int I = 0; I < NB; ++I)
+#pragma unroll
+        for (int J = I; J < NB; ++J, ++p)
+          if (p >= G * NPW && p < (G + 1) * NPW) {
+            if constexpr (SPLIT) are2[p - G * NPW] = mfma16(xi[I], xi[J], are2[p - G * NPW]);
+            else are[p - G * NPW] = mfma16(xi[I], xi[J], are[p - G * NPW]);
+            if (I != J) aim[p - G * NPW] = mfma16(-xr[I], xi[J], aim[p - G * NPW]);
+          }
+      if (++pending == (uint32_t)kDensFlush) {
+        flush();
+        pending = 0;
+      }
+    }
+  };
+  __syncthreads();  // the tables are written
+  if (blockIdx.x < d.ntiles) fetch(blockIdx.x);
+  for (uint64_t t = blockIdx.x; t < d.ntiles; t += gridDim.x) {
+    __syncthreads();  // the previous tile is consumed
+#pragma unroll
+    for (int i = 0; i < kPerLane; ++i) {
+      const uint32_t e = threadIdx.x + (uint32_t)i * kBlock;
+      if (e < tile_elems) tile[e ^ swz(e)] = held[i];
+    }
+    __syncthreads();
+    if (t + gridDim.x < d.ntiles) fetch(t + gridDim.x);
+    if (NG == 1 || grp == 0) steps(IntC<0>{});
+    else steps(IntC<NG - 1>{});
+  }
+  flush();
+  double* red = reinterpret_cast<double*>(lds);
+#pragma unroll
+  for (int part = 0; part < 2; ++part) {
+    for (uint32_t w = 0; w < (uint32_t)WG; ++w) {  // the waves of a group in wave order; the groups side by side
+      __syncthreads();
+      if (wi == w) {
+#pragma unroll
+        for (int p = 0; p < NPW; ++p)
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg) {
+            const uint32_t at = (grp * NPW + (uint32_t)p) * 256u + (uint32_t)reg * 64u + lane;
+            const double v = part ? tim[p][reg] : tre[p][reg];
+            red[at] = w ? red[at] + v : v;
+          }
+      }
+    }
+    __syncthreads();
+    for (uint32_t at = threadIdx.x; at < NPAIR * 256u; at += kBlock)
+      partial[(uint64_t)blockIdx.x * nout + (uint64_t)part * (NPAIR * 256u) + at] = red[at];
+  }
+}
+
 }  // namespace qipk

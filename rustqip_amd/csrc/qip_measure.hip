@@ -1036,6 +1036,261 @@ extern "C" int qipx_state_pauli_matrix_elements(qip_hip_state* bra, qip_hip_stat
   return ket->dtype == QIP_C64 ? pauli_melem_t<double>(ket, bra, terms, values) : pauli_melem_t<float>(ket, bra, terms, values);
 } QIP_CATCH_ALL
 
+// ---- reduced density matrices (include/qip_hipx.h) ----------------------------------------------------------------------
+//   sort    the kernels work on the positions in ascending order (bit j of their row index = the j-th lowest position)
+//   launch  k <= 3: k_density_small (register accumulators), k = 4 .. 6: k_density_mfma (matrix cores); one partial matrix per
+//           block in d_partial, the entries a <= a' only
+//   fold    k_sum_partials adds the blocks of every entry in block order on the device; 4^k doubles come back
+//   mirror  the host moves the sorted entries to the caller's bit order and writes the conjugates
+namespace {
+constexpr uint32_t kDensityMaxK = 6;
+constexpr unsigned kDensitySmallBlocks = 4096;  // lane chains of 2^(n-k-20) groups: 512 at n = 30, k = 1
+constexpr unsigned kDensityMfmaBlocks = 1024;   // 4 / 12 / 40 KiB of partials per block at k = 4 / 5 / 6: at most 40 MiB
+struct DensityGeom {
+  bool packed, b0;
+  uint32_t shift, ne;         // packed: positions in 16-byte elements of two amplitudes, ne = n - 1
+  std::vector<uint32_t> pe;   // the positions in elements, ascending (the half bit left out)
+};
+}  // namespace
+
+template <typename T>
+static DensityGeom density_geom(const qip_hip_state* s, const std::vector<uint32_t>& sorted) {
+  DensityGeom g;
+  g.packed = std::is_same<T, float>::value && s->packed_f32 && s->n >= 2;
+  g.shift = g.packed ? 1u : 0u;
+  g.ne = s->n - g.shift;
+  g.b0 = g.packed && sorted[0] == 0;
+  for (uint32_t p : sorted)
+    if (!(g.packed && p == 0)) g.pe.push_back(p - g.shift);
+  return g;
+}
+
+template <typename T, int KE, int KL, bool B0>
+static void density_small_launch(qip_hip_state* s, const DensityGeom& g, unsigned gx, const Ins& ins, const DensDesc& d) {
+  if constexpr (std::is_same<T, float>::value) {
+    if (g.packed) {
+      hipLaunchKernelGGL((k_density_small<float, KE, KL, B0, f32x4>), dim3(gx), dim3(kBlock), 0, s->stream, (const f32x4*)s->cur, ins, d, s->d_partial);
+      return;
+    }
+  }
+  if constexpr (!B0)
+    hipLaunchKernelGGL((k_density_small<T, KE, KL, false>), dim3(gx), dim3(kBlock), 0, s->stream, (const amp_t<T>*)s->cur, ins, d, s->d_partial);
+}
+
+template <typename T, int KE, bool B0>
+static void density_small_kl(qip_hip_state* s, const DensityGeom& g, uint32_t kl, unsigned gx, const Ins& ins, const DensDesc& d) {
+  switch (kl) {
+    case 0: density_small_launch<T, KE, 0, B0>(s, g, gx, ins, d); break;
+    case 1: if constexpr (KE >= 1) density_small_launch<T, KE, 1, B0>(s, g, gx, ins, d); break;
+    case 2: if constexpr (KE >= 2) density_small_launch<T, KE, 2, B0>(s, g, gx, ins, d); break;
+    default: if constexpr (KE >= 3) density_small_launch<T, KE, 3, B0>(s, g, gx, ins, d); break;
+  }
+}
+
+// `up`: the entries a <= a' of the matrix in sorted bit order, up[2 (a M + a')] and up[.. + 1] (the rest zero)
+template <typename T>
+static int density_small_t(qip_hip_state* s, const std::vector<uint32_t>& sorted, std::vector<double>* up) {
+  const DensityGeom g = density_geom<T>(s, sorted);
+  const uint32_t k = (uint32_t)sorted.size(), ke = (uint32_t)g.pe.size(), M = 1u << k;
+  DensDesc d;
+  memset(&d, 0, sizeof d);
+  uint32_t kl = 0;
+  std::vector<uint32_t> high;
+  for (uint32_t p : g.pe) {
+    if (p < 6) d.lpos[kl++] = p;
+    else high.push_back(p);
+  }
+  const uint32_t kh = ke - kl;
+  for (uint32_t c = 0; c < (1u << kh); ++c)
+    for (uint32_t i = 0; i < kh; ++i)
+      if ((c >> i) & 1u) d.coff[c] |= 1ull << high[i];
+  const uint64_t items = 1ull << (g.ne - kh);
+  d.nrows = std::max<uint64_t>(items >> 6, 1);
+  d.nlane = (uint32_t)std::min<uint64_t>(items, 64);
+  const uint64_t rows_per_wave_round = (uint64_t)(1u << kl) * ((1u << ke) >= 4u ? 1u : 4u >> ke);
+  const unsigned gx = (unsigned)std::min<uint64_t>(std::max<uint64_t>(d.nrows / (rows_per_wave_round * (kBlock / 64)), 1), kDensitySmallBlocks);
+  const size_t nout = (size_t)M * M;
+  QCHK(ensure_partial(s, (size_t)gx * nout + nout));
+  const Ins ins = make_ins(high, 0);
+  if (g.b0) {
+    if constexpr (std::is_same<T, float>::value) {
+      switch (ke) {
+        case 0: density_small_kl<float, 0, true>(s, g, kl, gx, ins, d); break;
+        case 1: density_small_kl<float, 1, true>(s, g, kl, gx, ins, d); break;
+        default: density_small_kl<float, 2, true>(s, g, kl, gx, ins, d); break;
+      }
+    }
+  } else {
+    switch (ke) {
+      case 1: density_small_kl<T, 1, false>(s, g, kl, gx, ins, d); break;
+      case 2: density_small_kl<T, 2, false>(s, g, kl, gx, ins, d); break;
+      default: density_small_kl<T, 3, false>(s, g, kl, gx, ins, d); break;
+    }
+  }
+  HIPCHK(hipGetLastError());
+  const double* res = s->d_partial;
+  if (gx > 1) {
+    hipLaunchKernelGGL((k_sum_partials<64>), dim3(grid_for(nout, kBlock / 64)), dim3(kBlock), 0, s->stream, s->d_partial, (uint32_t)gx,
+                       (uint64_t)nout, s->d_partial + (size_t)gx * nout);
+    HIPCHK(hipGetLastError());
+    res = s->d_partial + (size_t)gx * nout;
+  }
+  std::vector<double> part(nout);
+  HIPCHK(hipMemcpyAsync(part.data(), res, nout * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  up->assign(2 * nout, 0.0);
+  size_t p = 0;
+  for (uint32_t a = 0; a < M; ++a) {
+    (*up)[2 * ((size_t)a * M + a)] = part[a];
+    for (uint32_t a2 = a + 1; a2 < M; ++a2, ++p) {
+      (*up)[2 * ((size_t)a * M + a2)] = part[M + 2 * p];
+      (*up)[2 * ((size_t)a * M + a2) + 1] = part[M + 2 * p + 1];
+    }
+  }
+  return QIP_OK;
+}
+
+template <typename T, int K>
+static void density_mfma_launch(qip_hip_state* s, const DensityGeom& g, unsigned gx, const Ins& ins, const DensTileDesc& d, uint64_t nout) {
+  if constexpr (std::is_same<T, float>::value) {
+    if (g.packed) {
+      hipLaunchKernelGGL((k_density_mfma<float, K, f32x4>), dim3(gx), dim3(kBlock), 0, s->stream, (const f32x4*)s->cur, ins, d, nout, s->d_partial);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((k_density_mfma<T, K>), dim3(gx), dim3(kBlock), 0, s->stream, (const amp_t<T>*)s->cur, ins, d, nout, s->d_partial);
+}
+
+template <typename T>
+static int density_mfma_t(qip_hip_state* s, const std::vector<uint32_t>& sorted, std::vector<double>* up) {
+  const DensityGeom g = density_geom<T>(s, sorted);
+  const uint32_t k = (uint32_t)sorted.size(), ke = (uint32_t)g.pe.size(), M = 1u << k;
+  auto below = [&](uint32_t L) {
+    uint32_t c = 0;
+    for (uint32_t p : g.pe) c += p < L ? 1u : 0u;
+    return c;
+  };
+  // the longest run of 2^L elements whose tile, (the values of the positions >= L) x (one run), holds at most 2^11 elements (32 KiB
+  // of Complex<f64>): few barriers per byte and long contiguous reads.  L + (positions >= L) never falls as L grows.
+  uint32_t L = std::min<uint32_t>(5, g.ne);  // (six positions above a run of 2^5 elements: 2^11)
+  while (L < g.ne && (L + 1) + (ke - below(L + 1)) <= 11) ++L;
+  DensTileDesc d;
+  memset(&d, 0, sizeof d);
+  d.L = L;
+  std::vector<uint32_t> high;
+  for (uint32_t p : g.pe) {
+    if (p < L) d.rowmask |= 1u << (p + g.shift);
+    else high.push_back(p);
+  }
+  if (g.b0) d.rowmask |= 1u;
+  d.kh = (uint32_t)high.size();
+  for (uint32_t c = 0; c < (1u << d.kh); ++c)
+    for (uint32_t i = 0; i < d.kh; ++i)
+      if ((c >> i) & 1u) d.hoff[c] |= 1ull << high[i];
+  d.la = L + g.shift;
+  d.kla = k - d.kh;
+  d.lcols = d.la - d.kla;
+  for (uint32_t j = 0; j < 4; ++j) d.sw_src[j] = 31;  // (an unused pair: no slot has bit 31)
+  if (g.packed || std::is_same<T, double>::value) {  // 16-byte elements: the LDS swizzle of DensTileDesc
+    uint32_t occupied = 0, outside[4], nout_bits = 0, seen = 0;
+    for (uint32_t j = 0; j < 4; ++j) {  // row bit j of a 16-row block = the j-th lowest position
+      uint32_t tb = d.la + (j - d.kla);
+      if (j < d.kla) {
+        uint32_t m = d.rowmask;
+        for (uint32_t i = 0; i < j; ++i) m &= m - 1u;
+        tb = (uint32_t)__builtin_ctz(m);
+      }
+      if (tb < g.shift) continue;  // the half of a packed element: inside a slot
+      const uint32_t sb = tb - g.shift;
+      if (sb < 4) occupied |= 1u << sb;
+      else outside[nout_bits++] = sb;
+    }
+    for (uint32_t b = 0; b < 4 && seen < nout_bits; ++b)
+      if (!((occupied >> b) & 1u)) {
+        d.sw_src[d.nsw] = outside[seen++];
+        d.sw_dst[d.nsw++] = b;
+      }
+  }
+  d.ntiles = 1ull << (g.ne - L - d.kh);
+  const uint32_t NB = M / 16, npair = NB * (NB + 1) / 2;
+  const size_t nout = (size_t)npair * 512;
+  const unsigned gx = (unsigned)std::min<uint64_t>(d.ntiles, kDensityMfmaBlocks);
+  QCHK(ensure_partial(s, (size_t)gx * nout + nout));
+  const Ins ins = make_ins(high, 0);
+  switch (k) {
+    case 4: density_mfma_launch<T, 4>(s, g, gx, ins, d, nout); break;
+    case 5: density_mfma_launch<T, 5>(s, g, gx, ins, d, nout); break;
+    default: density_mfma_launch<T, 6>(s, g, gx, ins, d, nout); break;
+  }
+  HIPCHK(hipGetLastError());
+  const double* res = s->d_partial;
+  if (gx > 1) {
+    hipLaunchKernelGGL((k_sum_partials<64>), dim3(grid_for(nout, kBlock / 64)), dim3(kBlock), 0, s->stream, s->d_partial, (uint32_t)gx,
+                       (uint64_t)nout, s->d_partial + (size_t)gx * nout);
+    HIPCHK(hipGetLastError());
+    res = s->d_partial + (size_t)gx * nout;
+  }
+  std::vector<double> part(nout);
+  HIPCHK(hipMemcpyAsync(part.data(), res, nout * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  // C/D layout: entry (row i = (lane >> 4) + 4 reg, column j = lane & 15) of block pair p sits at p * 256 + reg * 64 + lane
+  auto at = [&](uint32_t part_no, uint32_t p, uint32_t i, uint32_t j) {
+    return part[((size_t)part_no * npair + p) * 256 + (size_t)(i >> 2) * 64 + (size_t)(i & 3u) * 16 + j];
+  };
+  up->assign(2 * (size_t)M * M, 0.0);
+  uint32_t p = 0;
+  for (uint32_t I = 0; I < NB; ++I)
+    for (uint32_t J = I; J < NB; ++J, ++p)
+      for (uint32_t i = 0; i < 16; ++i)
+        for (uint32_t j = (I == J ? i : 0u); j < 16; ++j) {
+          const size_t o = 2 * ((size_t)(16 * I + i) * M + 16 * J + j);
+          (*up)[o] = at(0, p, i, j);
+          if (I != J) (*up)[o + 1] = at(1, p, i, j);
+          else if (i != j) (*up)[o + 1] = at(1, p, i, j) - at(1, p, j, i);  // T - T^T, T = Xi Xr^T
+        }
+  return QIP_OK;
+}
+
+extern "C" int qipx_state_reduced_density(qip_hip_state* s, const uint64_t* indices, uint32_t k, double* rho) try {
+  STATE_ENTER_RAW(s);
+  if (!rho) return fail(QIP_ERR_INVALID, "reduced_density: null output");
+  MeasDesc md;
+  std::vector<uint32_t> pos;
+  QCHK(check_measure_indices(s, indices, k, &md, &pos));
+  if (k > kDensityMaxK) return fail(QIP_ERR_UNSUPPORTED, "reduced_density over k = %u qubits (at most %u)", k, kDensityMaxK);
+  if (!s->layout.empty()) QCHK(state_settle(s));  // a relabelled state: the caller's order first (nothing was launched before)
+  // bit j of the kernels' row index = the j-th lowest position = bit perm[j] of the caller's
+  std::vector<uint32_t> perm(k);
+  for (uint32_t i = 0; i < k; ++i) perm[i] = i;
+  std::sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return pos[a] < pos[b]; });
+  std::vector<uint32_t> sorted(k);
+  for (uint32_t j = 0; j < k; ++j) sorted[j] = pos[perm[j]];
+  std::vector<double> up;
+  if (k <= 3) QCHK(s->dtype == QIP_C64 ? density_small_t<double>(s, sorted, &up) : density_small_t<float>(s, sorted, &up));
+  else QCHK(s->dtype == QIP_C64 ? density_mfma_t<double>(s, sorted, &up) : density_mfma_t<float>(s, sorted, &up));
+  const uint32_t M = 1u << k;
+  std::vector<uint32_t> to_caller(M);
+  for (uint32_t a = 0; a < M; ++a) {
+    uint32_t c = 0;
+    for (uint32_t j = 0; j < k; ++j) c |= ((a >> j) & 1u) << perm[j];
+    to_caller[a] = c;
+  }
+  for (uint32_t a = 0; a < M; ++a) {
+    const uint32_t ca = to_caller[a];
+    rho[2 * ((size_t)ca * M + ca)] = up[2 * ((size_t)a * M + a)];
+    rho[2 * ((size_t)ca * M + ca) + 1] = 0.0;
+    for (uint32_t a2 = a + 1; a2 < M; ++a2) {
+      const uint32_t cb = to_caller[a2];
+      const double re = up[2 * ((size_t)a * M + a2)], im = up[2 * ((size_t)a * M + a2) + 1];
+      rho[2 * ((size_t)ca * M + cb)] = re;
+      rho[2 * ((size_t)ca * M + cb) + 1] = im;
+      rho[2 * ((size_t)cb * M + ca)] = re;
+      rho[2 * ((size_t)cb * M + ca) + 1] = -im;
+    }
+  }
+  return QIP_OK;
+} QIP_CATCH_ALL
+
 extern "C" int qip_hip_state_measure(qip_hip_state* s, const uint64_t* indices, uint32_t k,
                                      int64_t forced, double rand_u01, uint64_t* measured, double* prob) try {
   STATE_ENTER(s);

@@ -453,6 +453,18 @@ template <typename P> class HipState {
   }
   /// <*this|other> = sum_j conj((*this)[j]) other[j]: pauli_matrix_elements with the empty term
   std::complex<double> inner(HipState& other) { return pauli_matrix_elements(other, {{}})[0]; }
+  /// The raw reduced density matrix of up to six qubits (qip_hipx.h), row-major with M = 2^k:
+  /// out[a * M + a'] = sum_b psi[a,b] conj(psi[a',b]), bit i of a = qubit indices[i]; not divided by the norm; the lower triangle
+  /// is the exact conjugate of the upper.  The state is not changed.
+  std::vector<std::complex<double>> reduced_density_matrix(const std::vector<size_t>& indices) {
+    std::vector<uint64_t> idx(indices.begin(), indices.end());
+    const size_t m = size_t(1) << std::min<size_t>(idx.size(), 6);
+    std::vector<double> flat(2 * m * m);
+    check(qipx_state_reduced_density(h_, idx.data(), (uint32_t)idx.size(), flat.data()));
+    std::vector<std::complex<double>> out(m * m);
+    for (size_t t = 0; t < out.size(); ++t) out[t] = {flat[2 * t], flat[2 * t + 1]};
+    return out;
+  }
   std::vector<double> measure_probs(const std::vector<size_t>& indices) const {
     std::vector<uint64_t> idx(indices.begin(), indices.end());
     std::vector<double> out(size_t(1) << idx.size());

@@ -234,6 +234,21 @@ def pauli_sum_passes(n: int, terms, group: int = 0) -> int:
     return int(out.value)
 
 
+def von_neumann_entropy(rho, base: float = 2.0) -> float:
+    """The von Neumann entropy -tr(r log r) of r = rho / tr rho, in units of log `base` (2: bits).  `rho` is a Hermitian matrix
+    that need not be normalised (HipState.reduced_density_matrix returns the raw one).  Host only: numpy.linalg.eigvalsh;
+    eigenvalues <= 0 (rounding) count as 0, with 0 log 0 = 0."""
+    rho = np.asarray(rho, dtype=np.complex128)
+    if rho.ndim != 2 or rho.shape[0] != rho.shape[1]:
+        raise ValueError(f"a square matrix is needed, not shape {rho.shape}")
+    trace = float(np.trace(rho).real)
+    if not trace > 0.0:
+        raise ValueError("the matrix has no positive trace")
+    lam = np.linalg.eigvalsh(rho) / trace
+    lam = lam[lam > 0.0]
+    return float(-np.sum(lam * np.log(lam)) / np.log(base))
+
+
 def _u64_array(values: Sequence[int]):
     arr = (C.c_uint64 * len(values))(*[int(v) for v in values])
     return arr
@@ -500,6 +515,41 @@ class HipState:
     def inner(self, other: "HipState") -> complex:
         """<self|other> = sum_j conj(self[j]) other[j]: pauli_matrix_elements with the empty term"""
         return complex(self.pauli_matrix_elements(other, [{}])[0])
+
+    def reduced_density_matrix(self, indices: Sequence[int]) -> np.ndarray:
+        """complex128[2^k, 2^k]: rho[a, a'] = sum_b psi[a,b] conj(psi[a',b]), the reduced density matrix of the k <= 6 qubits
+        `indices` (include/qip_hipx.h), computed on the device in double for both precisions.  Bit i of a is the bit of qubit
+        indices[i], as in measure_probs.  Raw: not divided by the norm, so the trace is norm_sqr() and the diagonal is
+        measure_probs(indices).  The lower triangle is the exact conjugate of the upper.  The state is not changed."""
+        indices = [int(q) for q in indices]
+        k = len(indices)
+        out = np.zeros((1 << min(k, 6), 1 << min(k, 6)), dtype=np.complex128)
+        _check(_ffi.lib.qipx_state_reduced_density(self._h, _u64_array(indices), k, out.view(np.float64).ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def purity(self, indices: Sequence[int]) -> float:
+        """tr rho^2 / (tr rho)^2 of the reduced density matrix of `indices`: 1 for a product state, 2^-k when maximally mixed"""
+        rho = self.reduced_density_matrix(indices)
+        return float(np.sum(rho.real ** 2 + rho.imag ** 2) / np.trace(rho).real ** 2)  # (tr rho^2 = sum |rho_ij|^2: Hermitian)
+
+    def entanglement_entropy(self, indices: Sequence[int], base: float = 2.0) -> float:
+        """The von Neumann entropy of the qubits `indices` with the rest traced out, in units of log `base`.  More than six
+        qubits are traded for their complement when that has at most six (the state is pure: both sides share one spectrum);
+        otherwise the library's refusal is raised (QipHipError)."""
+        indices = [int(q) for q in indices]
+        if len(indices) > 6 and len(set(indices)) == len(indices) and all(0 <= q < self.n for q in indices) and self.n - len(indices) <= 6:
+            rest = [q for q in range(self.n) if q not in set(indices)]
+            if not rest:
+                return 0.0  # the whole of a pure state
+            indices = rest
+        return von_neumann_entropy(self.reduced_density_matrix(indices), base)
+
+    def mutual_information(self, a: Sequence[int], b: Sequence[int], base: float = 2.0) -> float:
+        """S(A) + S(B) - S(A u B) for two disjoint sets of qubits"""
+        a, b = [int(q) for q in a], [int(q) for q in b]
+        if set(a) & set(b):
+            raise ValueError(f"the two sets share qubits {sorted(set(a) & set(b))}")
+        return self.entanglement_entropy(a, base) + self.entanglement_entropy(b, base) - self.entanglement_entropy(a + b, base)
 
     def adjoint_gradient(self, rot_terms, angles, obs_terms, obs_coeffs, work: "HipState") -> Tuple[float, np.ndarray]:
         """(E, float64[T]): the energy E = <psi_T| H |psi_T> and its gradient with respect to the T angles, for
