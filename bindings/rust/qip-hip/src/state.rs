@@ -229,6 +229,42 @@ impl<P: HipPrecision> HipState<P> {
         check(unsafe { sys_ext::qipx_state_reduced_density(self.h, indices.as_ptr(), indices.len() as u32, flat.as_mut_ptr()) })?;
         Ok(flat.chunks(2 * m).map(|row| row.chunks(2).map(|c| (c[0], c[1])).collect()).collect())
     }
+    /// `self[j] <- own * self[j] + sum_i coeffs[i] * others[i][j]` in one pass (`include/qip_hipx.h`), coefficients as
+    /// `(re, im)`: `self` is the first source when `own` is given (two `&mut` to one state cannot be had, so the state itself
+    /// is named this way), at most 16 sources in all, none: `self <- 0`.  With `want_norm` the pass also returns
+    /// `sum_j |self[j]|^2` of the stored amplitudes.  Complete when it returns.
+    pub fn linear_combination(&mut self, own: Option<(f64, f64)>, others: &mut [&mut HipState<P>], coeffs: &[(f64, f64)], want_norm: bool) -> Result<Option<f64>, HipError> {
+        assert_eq!(others.len(), coeffs.len(), "one coefficient per source");
+        let mut handles: Vec<*mut sys::qip_hip_state> = Vec::new();
+        let mut flat: Vec<f64> = Vec::new();
+        if let Some((re, im)) = own {
+            handles.push(self.h);
+            flat.extend_from_slice(&[re, im]);
+        }
+        for (s, &(re, im)) in others.iter().zip(coeffs) {
+            handles.push(s.h);
+            flat.extend_from_slice(&[re, im]);
+        }
+        let count = handles.len() as u32;
+        handles.push(std::ptr::null_mut());
+        flat.push(0.0);
+        let mut norm = 0f64;
+        check(unsafe {
+            sys_ext::qipx_state_linear_combination(self.h, handles.as_ptr(), flat.as_ptr(), count, if want_norm { &mut norm } else { std::ptr::null_mut() })
+        })?;
+        Ok(if want_norm { Some(norm) } else { None })
+    }
+    /// `<bras[i]|self>` as `(re, im)` for up to 16 states in one pass over all of them (`include/qip_hipx.h`), in double for both
+    /// precisions; a batch equals its single-bra calls bit for bit.  No state is changed.
+    pub fn inner_products(&mut self, bras: &mut [&mut HipState<P>]) -> Result<Vec<(f64, f64)>, HipError> {
+        let mut handles: Vec<*mut sys::qip_hip_state> = bras.iter().map(|b| b.h).collect();
+        let count = handles.len() as u32;
+        handles.push(std::ptr::null_mut());
+        let mut flat = vec![0f64; 2 * bras.len() + 1];
+        check(unsafe { sys_ext::qipx_state_inner_products(handles.as_ptr(), count, self.h, flat.as_mut_ptr()) })?;
+        flat.truncate(2 * bras.len());
+        Ok(flat.chunks(2).map(|c| (c[0], c[1])).collect())
+    }
     pub fn raw(&mut self) -> *mut sys::qip_hip_state {
         self.h
     }

@@ -94,4 +94,17 @@ extern "C" {
     /// rho[2 (a M + a')] + i rho[.. + 1] = sum_b psi[a,b] conj(psi[a',b]), M = 2^k, 1 <= k <= 6: the raw reduced density matrix of
     /// the qubits `indices` (bit i of a = qubit indices[i]), in double for both precisions.  The state is not changed.
     pub fn qipx_state_reduced_density(s: *mut qip_hip_state, indices: *const u64, k: u32, rho: *mut c_double) -> c_int;
+    /// dst[j] <- sum_i (coeffs[2i] + i coeffs[2i+1]) srcs[i][j], 1 <= count <= 16 (0: dst <- 0), in the state's precision; dst may
+    /// be any of the sources.  A non-null `norm_sqr` receives sum_j |dst[j]|^2 of the stored values from the same pass.  Complete
+    /// when it returns.
+    pub fn qipx_state_linear_combination(
+        dst: *mut qip_hip_state,
+        srcs: *const *mut qip_hip_state,
+        coeffs: *const c_double,
+        count: u32,
+        norm_sqr: *mut c_double,
+    ) -> c_int;
+    /// values[2i] + i values[2i+1] = <bras[i]|ket>, 1 <= count <= 16, in double for both precisions, one pass over all of them; a
+    /// batch equals its single-bra calls bit for bit.  No state is changed.
+    pub fn qipx_state_inner_products(bras: *const *mut qip_hip_state, count: u32, ket: *mut qip_hip_state, values: *mut c_double) -> c_int;
 }

@@ -249,6 +249,67 @@ int qipx_state_pauli_matrix_elements(qip_hip_state* bra, qip_hip_state* ket, con
  * entry, as by the measurement calls.  The call is ordered after the work queued on the handle and complete when it returns. */
 int qipx_state_reduced_density(qip_hip_state* s, const uint64_t* indices, uint32_t k, double* rho);
 
+/* Vector arithmetic of resident states: what Lanczos and Krylov iterations need besides qipx_state_apply_pauli_sum.  (Purely
+ * additive again.)
+ *
+ * dst[j] <- sum_{i < count} c_i * srcs[i][j],   c_i = coeffs[2i] + i coeffs[2i+1],   for every amplitude j.
+ *
+ * Shape.  1 <= count <= 16; more is QIP_ERR_UNSUPPORTED.  count == 0 sets dst to zero and *norm_sqr to 0 (null arrays allowed).
+ * `dst` may be any of the sources and a handle may appear more than once: the operation is elementwise, every source is read at
+ * j before j is stored.  So scaling in place is count = 1 with srcs[0] == dst, and the Lanczos update w <- w - a v - b v' is one
+ * call of three sources.
+ *
+ * Cost.  ONE kernel launch: every listed source is read once (16-byte accesses: one Complex<f64>, two Complex<f32>) and dst is
+ * written once, whatever is aliased: count + 1 vectors of traffic.  No atomics.
+ *
+ * Arithmetic.  Everything is formed in the state's precision (u = 2^-53, 2^-24), without fused multiply-add.  c_i is rounded once
+ * to that precision on the host, (cr, ci).  Per amplitude, with src_i[j] = (sr, si),
+ *   p_i = ( fl(fl(cr sr) - fl(ci si)),  fl(fl(cr si) + fl(ci sr)) ),
+ *   acc = p_0,  then  acc = fl(acc + p_i)  per component for i = 1 .. count-1 in source order,
+ * and acc is stored.  Zero, real and imaginary coefficients get no special case (a coefficient 0 still multiplies: a NaN or an
+ * infinity in that source spreads, and -0 can appear).  The result depends on the call only: same call, same bits.
+ *
+ * Norm.  With a non-null `norm_sqr` the same pass also returns sum_j |dst[j]|^2 of the STORED (rounded) amplitudes, formed in
+ * double for both precisions: each component is widened, fl(fl(x x) + fl(y y)) is added to the lane's running sum, then wave,
+ * block, and one partial per block in dst's reduction scratch, which the host adds in block order, as norm_sqr does.  The grid
+ * depends on n and the precision only: the same call returns the same bits, and the value is within 1e-12 times the exact sum
+ * (non-negative terms along chains of at most c = 2^(n-20) + 6 + 4 + 4096 additions — lane, wave tree, the block's waves, the
+ * host's blocks — which is 5130 at n = 30: (c + 2) 2^-53 = 5.7e-13).
+ * (qip_hip.h's norm_sqr forms |psi_j|^2 in the state's precision: on a Complex<f32> state the two agree to f32 rounding only.)
+ *
+ * Calling contract, as qipx_state_apply_pauli_sum's.  Every handle is put in the caller's order on entry (option "tile_relabel"
+ * = 3), the work queued on every source is waited for, the pass runs on dst's stream and THE CALL IS COMPLETE WHEN IT RETURNS.  No
+ * source other than dst is changed.  Each of these is refused with a message before anything is queued, dst untouched: a null
+ * handle, dst or a source (QIP_ERR_INVALID: there is no host fall-back); an unusable handle (QIP_ERR_DEVICE); a source that
+ * differs from dst in n or dtype (QIP_ERR_INVALID) or lives on another device (QIP_ERR_UNSUPPORTED); with count > 0 a null array
+ * or a non-finite coefficient (QIP_ERR_INVALID; the message names the source); count > 16 (QIP_ERR_UNSUPPORTED).
+ *
+ * There is no option: the kernel is compiled for 1, 2, 3, 4, 8 and 16 sources and a call takes the smallest that holds it. */
+int qipx_state_linear_combination(qip_hip_state* dst, qip_hip_state* const* srcs, const double* coeffs, uint32_t count,
+                                  double* norm_sqr /* may be null */);
+
+/* Inner products of up to 16 states with one state.  (Purely additive again.)
+ *
+ * values[2i] + i values[2i+1] = <bras[i]|ket> = sum_j conj(bras[i][j]) * ket[j],   i < count.
+ *
+ * Shape.  1 <= count <= 16; more is QIP_ERR_UNSUPPORTED, count == 0 returns QIP_OK (null arrays allowed).  ONE pass reads `ket`
+ * once and each bra once (16-byte accesses): orthogonalising against a basis of m vectors moves m + 1 vectors, not 2m.
+ * bras[i] == ket is allowed, and then values[2i+1] is exactly +0: the two products of the imaginary part are the same numbers.
+ *
+ * Precision.  Products and sums are formed in double for both precisions; f32 amplitudes are widened before the first product.
+ * With bra[j] = (pr, pi) and ket[j] = (ar, ai) an amplitude adds fl(fl(pr ar) + fl(pi ai)) and fl(fl(pr ai) - fl(pi ar)) to the
+ * lane's two running sums; then wave, block, one partial per block in ket's reduction scratch, added on the host in block
+ * order.  No atomics.  Each part is within (c + 2) 2^-53 sum_j |bra[j]| |ket[j]| <= 5.7e-13 |bra| |ket| of the exact sum for
+ * n <= 30 (c as above; Cauchy-Schwarz).
+ *
+ * Reproducibility.  values[2i], values[2i+1] depend on bras[i] and ket only: there is one grid and one accumulation order per n
+ * and precision whatever `count` is, so a batch equals its single-bra calls bit for bit.  The bits are NOT those of
+ * qipx_state_pauli_matrix_elements with the empty term: that call keeps its kernel and its order.
+ *
+ * Neither state is changed.  The handles are met as above (ket in the place of dst), the call is ordered after the work queued
+ * on all of them and complete when it returns.  With count > 0 a null `bras` or `values` is QIP_ERR_INVALID. */
+int qipx_state_inner_products(qip_hip_state* const* bras, uint32_t count, qip_hip_state* ket, double* values);
+
 #ifdef __cplusplus
 }
 #endif

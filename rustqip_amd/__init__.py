@@ -15,6 +15,7 @@ from .state import (HipState, QipHipError, apply_op, apply_op_device, apply_op_o
                     make_op_matrix, set_global_option)
 from .builder import Conditioned, HipBuilder, Measurements, Register, lower_to_matrix_op
 from .state import DeviceSlice, HipProgram, expect_pauli_passes, ext_abi_version, pauli_rotation_passes, pauli_sum_passes, von_neumann_entropy
+from .state import krylov_bar, tridiagonal_eigh, tridiagonal_propagator_column
 from . import circuits  # noqa: F401  (workload generators: rustqip_amd.circuits)
 from . import replay  # noqa: F401  (flat circuit-replay format)
 
@@ -23,5 +24,5 @@ __all__ = [
     "make_matrix_op", "make_sparse_matrix_op", "make_swap_op", "validate_op", "HipState", "QipHipError",
     "apply_op", "apply_op_device", "apply_op_overwrite", "apply_op_row", "device_count", "make_op_matrix", "set_global_option", "Conditioned",
     "HipBuilder", "Measurements", "Register", "lower_to_matrix_op", "HipProgram", "DeviceSlice", "circuits", "replay", "ext_abi_version", "expect_pauli_passes",
-    "pauli_rotation_passes", "pauli_sum_passes", "von_neumann_entropy",
+    "pauli_rotation_passes", "pauli_sum_passes", "von_neumann_entropy", "krylov_bar", "tridiagonal_eigh", "tridiagonal_propagator_column",
 ]

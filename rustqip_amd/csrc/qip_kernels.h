@@ -3455,6 +3455,131 @@ __global__ __launch_bounds__(kBlock) void k_pauli_melem(const E* __restrict__ br
   }
 }
 
+// ---- vector arithmetic of resident states: dst <- sum_i c_i src_i and <bra_i|ket> (qipx_state_linear_combination,
+// qipx_state_inner_products, include/qip_hipx.h) -------------------------------------------------------------------------------
+// Elementwise grid-stride passes over 16-byte elements (one Complex<f64>, or two packed Complex<f32>: n >= 1, so a Complex<f32>
+// state is a whole number of them).  The source pointers travel by value in the descriptor, as SumDesc's coefficients do; slot g
+// of a capacity G is compiled in and skipped by a wave-uniform test when g >= count.  A lane keeps the G loads of an element in
+// flight together (U elements of them when G is small: U * G >= 4 loads, k_chunk_norms' depth), then does the arithmetic, then
+// stores: every source is read at j before j is stored, so `dst` may be any of the sources and no pointer is __restrict__.
+// The grid depends on the number of elements only (vec_grid on the host) and a lane meets its elements in ascending order
+// whatever U is, so every sum below has ONE order per n and precision.
+constexpr int kVecMax = 16;
+template <typename T> struct LincombDesc {
+  const void* src[kVecMax];
+  T cr[kVecMax], ci[kVecMax];  // c_i, rounded once to T on the host
+  uint32_t count;              // slots in use
+};
+struct InnerDesc {
+  const void* bra[kVecMax];
+  uint32_t count;
+};
+constexpr int vec_unroll(int loads) { return loads >= 4 ? 1 : 4 / loads; }
+
+// acc <- [FIRST ? 0 : acc] + c * s per component: two products, one difference / sum, one add, never fused
+template <bool FIRST, typename T> __device__ __forceinline__ void lincomb_put(T cr, T ci, T sr, T si, T& ar, T& ai) {
+  const T pr = cr * sr - ci * si, pi = cr * si + ci * sr;
+  ar = FIRST ? pr : ar + pr;
+  ai = FIRST ? pi : ai + pi;
+}
+
+// dst[j] <- sum_{g < count} c_g src_g[j]: acc = p_0, then acc = fl(acc + p_g) in slot order.  NORM: partial[blockIdx.x] = the
+// block's share of sum_j |dst[j]|^2 of the STORED values, widened to double before the squares (k_pauli_melem's scheme: lane,
+// wave, block, one partial per block; no atomics).
+template <typename T, int G, bool NORM, typename E = amp_t<T>>
+__global__ __launch_bounds__(kBlock) void k_lincomb(E* dst, uint64_t nelems, LincombDesc<T> d, double* __restrict__ partial) {
+  constexpr bool PACKED = !SameT<E, amp_t<T>>::v;
+  constexpr int U = vec_unroll(G);
+  __shared__ double smem[kBlock / 64];
+  double s = 0;
+  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+  for (uint64_t i0 = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i0 < nelems; i0 += U * stride) {
+    E x[U][G];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int g = 0; g < G; ++g)
+        if ((uint32_t)g < d.count && i0 + u * stride < nelems)
+          x[u][g] = __builtin_nontemporal_load((const E*)d.src[g] + (i0 + u * stride));
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint64_t i = i0 + u * stride;
+      if (i < nelems) {
+        T r0 = T(0), i0_ = T(0), r1 = T(0), i1 = T(0);
+        lincomb_put<true>(d.cr[0], d.ci[0], x[u][0].x, x[u][0].y, r0, i0_);
+        if constexpr (PACKED) lincomb_put<true>(d.cr[0], d.ci[0], x[u][0].z, x[u][0].w, r1, i1);
+#pragma unroll
+        for (int g = 1; g < G; ++g)
+          if ((uint32_t)g < d.count) {
+            lincomb_put<false>(d.cr[g], d.ci[g], x[u][g].x, x[u][g].y, r0, i0_);
+            if constexpr (PACKED) lincomb_put<false>(d.cr[g], d.ci[g], x[u][g].z, x[u][g].w, r1, i1);
+          }
+        E out;
+        out.x = r0, out.y = i0_;
+        if constexpr (PACKED) out.z = r1, out.w = i1;
+        __builtin_nontemporal_store(out, dst + i);
+        if constexpr (NORM) {
+          s += (double)r0 * (double)r0 + (double)i0_ * (double)i0_;
+          if constexpr (PACKED) s += (double)r1 * (double)r1 + (double)i1 * (double)i1;
+        }
+      }
+    }
+  }
+  if constexpr (NORM) {
+    const double t = block_reduce_sum(s, smem);
+    if (threadIdx.x == 0) partial[blockIdx.x] = t;
+  }
+}
+
+// partial[(2 g + c) * gridDim.x + blockIdx.x], c = 0 the real and 1 the imaginary part of the block's share of
+// sum_j conj(bra_g[j]) ket[j]: everything widened to double before the first product, re = fl(fl(pr ar) + fl(pi ai)),
+// im = fl(fl(pr ai) - fl(pi ar)) (so bra_g == ket gives an imaginary part of exactly +0), one running complex sum per slot, which
+// sees the same addends in the same order for every capacity G and whatever its company.
+template <typename T, int G, typename E = amp_t<T>>
+__global__ __launch_bounds__(kBlock) void k_inner_many(const E* ket, uint64_t nelems, InnerDesc d, double* __restrict__ partial) {
+  constexpr bool PACKED = !SameT<E, amp_t<T>>::v;
+  constexpr int U = vec_unroll(G + 1);
+  __shared__ double smem[kBlock / 64];
+  double accr[G], acci[G];
+#pragma unroll
+  for (int g = 0; g < G; ++g) accr[g] = acci[g] = 0.0;
+  auto add = [&](int g, double pr, double pi, double ar, double ai) {
+    accr[g] += pr * ar + pi * ai;
+    acci[g] += pr * ai - pi * ar;
+  };
+  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+  for (uint64_t i0 = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i0 < nelems; i0 += U * stride) {
+    E a[U], p[U][G];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (i0 + u * stride < nelems) {
+        a[u] = __builtin_nontemporal_load(ket + (i0 + u * stride));
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+          if ((uint32_t)g < d.count) p[u][g] = __builtin_nontemporal_load((const E*)d.bra[g] + (i0 + u * stride));
+      }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (i0 + u * stride < nelems) {
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+          if ((uint32_t)g < d.count) {
+            add(g, p[u][g].x, p[u][g].y, a[u].x, a[u].y);
+            if constexpr (PACKED) add(g, p[u][g].z, p[u][g].w, a[u].z, a[u].w);
+          }
+      }
+  }
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const double tr = block_reduce_sum(accr[g], smem);
+    const double ti = block_reduce_sum(acci[g], smem);
+    if (threadIdx.x == 0 && (uint32_t)g < d.count) {
+      partial[(uint64_t)(2 * g) * gridDim.x + blockIdx.x] = tr;
+      partial[(uint64_t)(2 * g + 1) * gridDim.x + blockIdx.x] = ti;
+    }
+  }
+}
+
 // Two states compared amplitude by amplitude over the whole vector (qip_hip_state_max_abs_diff: how far a state is from a
 // reference copy): partial[2 b] = max |a_i - b_i| over block b's share, partial[2 b + 1] = number of amplitudes whose
 // components are not IEEE-equal (NaNs count as different).  Grid-stride, one coalesced pass over both vectors.

@@ -1036,6 +1036,126 @@ extern "C" int qipx_state_pauli_matrix_elements(qip_hip_state* bra, qip_hip_stat
   return ket->dtype == QIP_C64 ? pauli_melem_t<double>(ket, bra, terms, values) : pauli_melem_t<float>(ket, bra, terms, values);
 } QIP_CATCH_ALL
 
+// ---- vector arithmetic of resident states: dst <- sum_i c_i src_i and <bra_i|ket> (include/qip_hipx.h) -------------------
+//   meet    every handle as the two-state calls above meet theirs (pair_meet, pair_settle), all refusals before anything is queued
+//   launch  ONE k_lincomb / k_inner_many launch in a grid that depends on the number of 16-byte elements only (vec_grid), in the
+//           smallest capacity of kVecCaps that holds the call
+//   fold    per-block partials in the own state's reduction scratch, added on the host in block order
+// Both calls are complete when they return.
+static unsigned vec_grid(uint64_t nelems) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>(nelems / (kBlock * 4), 1), 4096); }
+// 16-byte elements of a state: one Complex<f64>, two Complex<f32> (n >= 1: never half an element)
+static uint64_t vec_elems(const qip_hip_state* s) { return s->dtype == QIP_C64 ? s->namps : s->namps / 2; }
+
+template <typename T, int G, bool NORM>
+static void lincomb_launch_g(qip_hip_state* dst, const LincombDesc<T>& d, unsigned gx, uint64_t nelems) {
+  using E = typename std::conditional<std::is_same<T, float>::value, f32x4, amp_t<T>>::type;
+  hipLaunchKernelGGL((k_lincomb<T, G, NORM, E>), dim3(gx), dim3(kBlock), 0, dst->stream, (E*)dst->cur, nelems, d, dst->d_partial);
+}
+
+template <typename T, bool NORM>
+static void lincomb_launch(qip_hip_state* dst, const LincombDesc<T>& d, unsigned gx, uint64_t nelems) {
+  // the capacities: 1 to 4 sources each have their own (scale, axpy, the Lanczos update of three), then 8 and 16
+  if (d.count <= 1) lincomb_launch_g<T, 1, NORM>(dst, d, gx, nelems);
+  else if (d.count == 2) lincomb_launch_g<T, 2, NORM>(dst, d, gx, nelems);
+  else if (d.count == 3) lincomb_launch_g<T, 3, NORM>(dst, d, gx, nelems);
+  else if (d.count == 4) lincomb_launch_g<T, 4, NORM>(dst, d, gx, nelems);
+  else if (d.count <= 8) lincomb_launch_g<T, 8, NORM>(dst, d, gx, nelems);
+  else lincomb_launch_g<T, kVecMax, NORM>(dst, d, gx, nelems);
+}
+
+template <typename T>
+static int lincomb_t(qip_hip_state* dst, qip_hip_state* const* srcs, const double* coeffs, uint32_t count, double* norm_sqr) {
+  const uint64_t nelems = vec_elems(dst);
+  const unsigned gx = vec_grid(nelems);
+  LincombDesc<T> d;
+  memset(&d, 0, sizeof d);
+  d.count = count;
+  for (uint32_t i = 0; i < count; ++i) {
+    d.src[i] = srcs[i]->cur;
+    d.cr[i] = (T)coeffs[2 * (size_t)i];
+    d.ci[i] = (T)coeffs[2 * (size_t)i + 1];
+  }
+  if (norm_sqr) {
+    QCHK(ensure_partial(dst, gx));
+    lincomb_launch<T, true>(dst, d, gx, nelems);
+  } else {
+    lincomb_launch<T, false>(dst, d, gx, nelems);
+  }
+  HIPCHK(hipGetLastError());
+  std::vector<double> part(norm_sqr ? gx : 0);
+  if (norm_sqr) HIPCHK(hipMemcpyAsync(part.data(), dst->d_partial, gx * sizeof(double), hipMemcpyDeviceToHost, dst->stream));
+  HIPCHK(hipStreamSynchronize(dst->stream));  // complete on return: the caller may change a source at once
+  if (norm_sqr) {
+    double t = 0;
+    for (double v : part) t += v;
+    *norm_sqr = t;
+  }
+  return QIP_OK;
+}
+
+extern "C" int qipx_state_linear_combination(qip_hip_state* dst, qip_hip_state* const* srcs, const double* coeffs, uint32_t count,
+                                             double* norm_sqr) try {
+  STATE_ENTER_RAW(dst);
+  if (count > (uint32_t)kVecMax) return fail(QIP_ERR_UNSUPPORTED, "linear_combination: %u sources, at most %d are supported", count, kVecMax);
+  if (count > 0 && (!srcs || !coeffs)) return fail(QIP_ERR_INVALID, "linear_combination: null source or coefficient array");
+  for (uint32_t i = 0; i < count; ++i) QCHK(pair_meet("linear_combination", dst, srcs[i]));
+  for (uint32_t i = 0; i < count; ++i)
+    if (!std::isfinite(coeffs[2 * (size_t)i]) || !std::isfinite(coeffs[2 * (size_t)i + 1]))
+      return fail(QIP_ERR_INVALID, "linear_combination: the coefficient of source %u is not finite", i);
+  QCHK(pair_settle(dst, dst));
+  for (uint32_t i = 0; i < count; ++i) QCHK(pair_settle(dst, srcs[i]));
+  if (count == 0) {
+    HIPCHK(hipMemsetAsync(dst->cur, 0, dst->namps * dst->amp_bytes, dst->stream));
+    HIPCHK(hipStreamSynchronize(dst->stream));
+    if (norm_sqr) *norm_sqr = 0.0;
+    return QIP_OK;
+  }
+  return dst->dtype == QIP_C64 ? lincomb_t<double>(dst, srcs, coeffs, count, norm_sqr) : lincomb_t<float>(dst, srcs, coeffs, count, norm_sqr);
+} QIP_CATCH_ALL
+
+template <typename T, int G>
+static void inner_launch_g(qip_hip_state* ket, const InnerDesc& d, unsigned gx, uint64_t nelems) {
+  using E = typename std::conditional<std::is_same<T, float>::value, f32x4, amp_t<T>>::type;
+  hipLaunchKernelGGL((k_inner_many<T, G, E>), dim3(gx), dim3(kBlock), 0, ket->stream, (const E*)ket->cur, nelems, d, ket->d_partial);
+}
+
+template <typename T>
+static int inner_many_t(qip_hip_state* ket, qip_hip_state* const* bras, uint32_t count, double* values) {
+  const uint64_t nelems = vec_elems(ket);
+  const unsigned gx = vec_grid(nelems);
+  InnerDesc d;
+  memset(&d, 0, sizeof d);
+  d.count = count;
+  for (uint32_t i = 0; i < count; ++i) d.bra[i] = bras[i]->cur;
+  const size_t need = 2 * (size_t)count * gx;
+  QCHK(ensure_partial(ket, need));
+  if (count <= 1) inner_launch_g<T, 1>(ket, d, gx, nelems);
+  else if (count <= 2) inner_launch_g<T, 2>(ket, d, gx, nelems);
+  else if (count <= 4) inner_launch_g<T, 4>(ket, d, gx, nelems);
+  else if (count <= 8) inner_launch_g<T, 8>(ket, d, gx, nelems);
+  else inner_launch_g<T, kVecMax>(ket, d, gx, nelems);
+  HIPCHK(hipGetLastError());
+  std::vector<double> part(need);
+  HIPCHK(hipMemcpyAsync(part.data(), ket->d_partial, need * sizeof(double), hipMemcpyDeviceToHost, ket->stream));
+  HIPCHK(hipStreamSynchronize(ket->stream));
+  for (uint32_t i = 0; i < count; ++i) {
+    double re = 0, im = 0;
+    for (unsigned b = 0; b < gx; ++b) re += part[(size_t)(2 * i) * gx + b], im += part[(size_t)(2 * i + 1) * gx + b];
+    values[2 * (size_t)i] = re, values[2 * (size_t)i + 1] = im;
+  }
+  return QIP_OK;
+}
+
+extern "C" int qipx_state_inner_products(qip_hip_state* const* bras, uint32_t count, qip_hip_state* ket, double* values) try {
+  STATE_ENTER_RAW(ket);
+  if (count == 0) return QIP_OK;
+  if (count > (uint32_t)kVecMax) return fail(QIP_ERR_UNSUPPORTED, "inner_products: %u bras, at most %d are supported", count, kVecMax);
+  if (!bras || !values) return fail(QIP_ERR_INVALID, "inner_products: null bra or result array");
+  for (uint32_t i = 0; i < count; ++i) QCHK(pair_meet("inner_products", ket, bras[i]));
+  for (uint32_t i = 0; i < count; ++i) QCHK(pair_settle(ket, bras[i]));
+  return ket->dtype == QIP_C64 ? inner_many_t<double>(ket, bras, count, values) : inner_many_t<float>(ket, bras, count, values);
+} QIP_CATCH_ALL
+
 // ---- reduced density matrices (include/qip_hipx.h) ----------------------------------------------------------------------
 //   sort    the kernels work on the positions in ascending order (bit j of their row index = the j-th lowest position)
 //   launch  k <= 3: k_density_small (register accumulators), k = 4 .. 6: k_density_mfma (matrix cores); one partial matrix per

@@ -465,6 +465,30 @@ template <typename P> class HipState {
     for (size_t t = 0; t < out.size(); ++t) out[t] = {flat[2 * t], flat[2 * t + 1]};
     return out;
   }
+  /// *this[j] <- sum_i coeffs[i] * (*srcs[i])[j] in one pass (qip_hipx.h): up to 16 states of the same n, precision and device,
+  /// *this allowed among them; no sources: *this <- 0.  With `norm_sqr` the pass also returns sum_j |(*this)[j]|^2 of the stored
+  /// amplitudes.  Complete when it returns.
+  void linear_combination(const std::vector<HipState*>& srcs, const std::vector<std::complex<double>>& coeffs, double* norm_sqr = nullptr) {
+    if (coeffs.size() != srcs.size()) throw std::invalid_argument("linear_combination: one coefficient per source");
+    std::vector<qip_hip_state*> handles(srcs.size() + 1, nullptr);  // (never a null data())
+    std::vector<double> flat(2 * coeffs.size() + 1);
+    for (size_t i = 0; i < srcs.size(); ++i) {
+      handles[i] = srcs[i] ? srcs[i]->h_ : nullptr;
+      flat[2 * i] = coeffs[i].real(), flat[2 * i + 1] = coeffs[i].imag();
+    }
+    check(qipx_state_linear_combination(h_, handles.data(), flat.data(), (uint32_t)srcs.size(), norm_sqr));
+  }
+  /// <*bras[i]|*this> for up to 16 states in one pass over all of them (qip_hipx.h), in double for both precisions; a batch equals
+  /// its single-bra calls bit for bit.  No state is changed.
+  std::vector<std::complex<double>> inner_products(const std::vector<HipState*>& bras) {
+    std::vector<qip_hip_state*> handles(bras.size() + 1, nullptr);
+    for (size_t i = 0; i < bras.size(); ++i) handles[i] = bras[i] ? bras[i]->h_ : nullptr;
+    std::vector<double> flat(2 * bras.size() + 1);
+    check(qipx_state_inner_products(handles.data(), (uint32_t)bras.size(), h_, flat.data()));
+    std::vector<std::complex<double>> out(bras.size());
+    for (size_t i = 0; i < out.size(); ++i) out[i] = {flat[2 * i], flat[2 * i + 1]};
+    return out;
+  }
   std::vector<double> measure_probs(const std::vector<size_t>& indices) const {
     std::vector<uint64_t> idx(indices.begin(), indices.end());
     std::vector<double> out(size_t(1) << idx.size());

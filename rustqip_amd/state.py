@@ -249,6 +249,54 @@ def von_neumann_entropy(rho, base: float = 2.0) -> float:
     return float(-np.sum(lam * np.log(lam)) / np.log(base))
 
 
+# The constant of krylov_bar: 8 times the worst error ratio the solvers' numpy restatement shows in the state's own precision on
+# the test inputs, rounded up to a power of two (tests/krylov_ref.py has the measured ratios; profiles/krylov.md repeats them).
+KRYLOV_K = 0.25
+
+
+def krylov_bar(m: int, nterms: int, weight: float, dtype) -> float:
+    """B = KRYLOV_K * m * (T + 8) * u * S: what the Krylov solvers of HipState call zero — the breakdown threshold of
+    krylov_basis and the residual at which ground_state stops — for a basis of m + 1 states, a Hamiltonian of T = `nterms`
+    terms of weight S = sum |coeffs| and the unit roundoff u of `dtype` (2^-53 for complex128, 2^-24 for complex64)."""
+    u = 2.0 ** -24 if np.dtype(dtype) == np.dtype(np.complex64) else 2.0 ** -53
+    return KRYLOV_K * int(m) * (int(nterms) + 8) * u * float(weight)
+
+
+def _tridiagonal(alphas, betas) -> np.ndarray:
+    a = np.asarray(alphas, dtype=np.float64).reshape(-1)
+    b = np.asarray(betas, dtype=np.float64).reshape(-1)[:max(len(a) - 1, 0)]
+    if len(a) < 1 or len(b) != len(a) - 1:
+        raise ValueError(f"{len(a)} diagonal and {len(b)} off-diagonal entries are not a tridiagonal matrix")
+    return np.diag(a) + np.diag(b, 1) + np.diag(b, -1)
+
+
+def tridiagonal_eigh(alphas, betas):
+    """(theta, Y) of the k x k symmetric tridiagonal matrix with diagonal alphas[:k] and off-diagonal betas[:k - 1], k =
+    len(alphas) (a longer `betas`, as krylov_basis returns it, is cut): numpy.linalg.eigh, eigenvalues ascending, Y's columns
+    the eigenvectors."""
+    return np.linalg.eigh(_tridiagonal(alphas, betas))
+
+
+def tridiagonal_propagator_column(alphas, betas, tau: float) -> np.ndarray:
+    """complex128[k]: the first column of exp(-i T tau) for the tridiagonal matrix T of tridiagonal_eigh, by Taylor series in
+    s = ceil(|T|_1 |tau|) steps of tau / s, applied to e_0.  Entry i of the column is of the size (|T| tau)^i / i!, and the
+    last one is what krylov_evolve's error estimate is made of: the series keeps its RELATIVE accuracy (entry i is first
+    reached by the term of order i and the later terms fall off factorially; a step of norm <= 1 has no cancellation to speak
+    of), where the eigendecomposition sum_l Y[i, l] exp(-i theta_l tau) Y[0, l] leaves an absolute error of the unit roundoff
+    in every entry — noise of 100 % in an estimate that has converged."""
+    t = _tridiagonal(alphas, betas)
+    steps = max(1, int(np.ceil(np.max(np.sum(np.abs(t), axis=0)) * abs(float(tau)))))
+    step = -1j * float(tau) / steps
+    column = np.zeros(len(t), dtype=np.complex128)
+    column[0] = 1.0
+    for _ in range(steps):
+        term = column
+        for order in range(1, len(t) + 26):  # (|step T| <= 1: 25 orders beyond the one that reaches the last entry, 1 / 25! = 6e-26)
+            term = (step / order) * (t @ term)
+            column = column + term
+    return column
+
+
 def _u64_array(values: Sequence[int]):
     arr = (C.c_uint64 * len(values))(*[int(v) for v in values])
     return arr
@@ -586,6 +634,154 @@ class HipState:
             self.apply_pauli_rotations([rot_terms[k]], [-a[k]])
             work.apply_pauli_rotations([rot_terms[k]], [-a[k]])
         return float(energy), grad
+
+    # -- vector arithmetic and Krylov solvers (include/qip_hipx.h) -----------------------------------------------------
+    def _handles(self, states, what: str):
+        states = list(states)
+        for s in states:
+            self._partner(s, what)
+        return states, (C.c_void_p * max(len(states), 1))(*[s._h.value for s in states])
+
+    def linear_combination(self, srcs, coeffs, want_norm: bool = False) -> Optional[float]:
+        """self[j] <- sum_i coeffs[i] * srcs[i][j] in ONE pass (include/qip_hipx.h): up to 16 states of the same n, precision
+        and device, real or complex coefficients, arithmetic in the state's precision.  `self` may be among the sources and a
+        state may be listed twice.  No sources: self <- 0.  With `want_norm` the pass also returns sum_j |self[j]|^2 of the
+        stored amplitudes (in double); otherwise None.  Complete when it returns."""
+        srcs, handles = self._handles(srcs, "linear_combination")
+        c = np.ascontiguousarray(np.asarray(coeffs, dtype=np.complex128).reshape(-1))
+        if len(c) != len(srcs):
+            raise CircuitError(f"{len(srcs)} sources but {len(c)} coefficients")
+        c = np.concatenate([c, [0.0]])  # (never a null array for an empty list)
+        norm = C.c_double()
+        _check(_ffi.lib.qipx_state_linear_combination(self._h, handles, c.view(np.float64).ctypes.data_as(C.POINTER(C.c_double)),
+                                                      len(srcs), C.byref(norm) if want_norm else None))
+        return norm.value if want_norm else None
+
+    def inner_products(self, bras) -> np.ndarray:
+        """complex128[len(bras)]: <bras[i]|self> for up to 16 states in ONE pass over all of them (include/qip_hipx.h), in
+        double for both precisions.  A value does not depend on the other bras of the call; a bra may be `self` (its imaginary
+        part is then exactly 0).  No state is changed."""
+        bras, handles = self._handles(bras, "inner_products")
+        out = np.zeros(len(bras), dtype=np.complex128)
+        _check(_ffi.lib.qipx_state_inner_products(handles, len(bras), self._h, out.view(np.float64).ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def scale(self, c: complex) -> None:
+        """self <- c * self"""
+        self.linear_combination([self], [c])
+
+    def axpy(self, a: complex, x: "HipState") -> None:
+        """self <- self + a * x"""
+        self.linear_combination([self, x], [1.0, a])
+
+    def normalize(self) -> float:
+        """self <- self / |self|; returns the old norm |self| (one reading pass for it, one pass to scale)"""
+        norm = float(np.sqrt(self.inner_products([self])[0].real))
+        if not (norm > 0.0 and np.isfinite(norm)):
+            raise CircuitError(f"normalize: the state's norm is {norm}")
+        self.scale(1.0 / norm)
+        return norm
+
+    def _krylov_setup(self, terms, coeffs, basis, what: str):
+        """checks of the three solvers, all before anything is queued: (terms, float64 coefficients, basis, the bar B)"""
+        terms = list(terms)
+        c = np.asarray(coeffs)
+        if np.iscomplexobj(c):
+            raise CircuitError(f"{what}: the Hamiltonian's coefficients are real")
+        c = np.asarray(c, dtype=np.float64).reshape(-1)
+        if len(c) != len(terms):
+            raise CircuitError(f"{len(terms)} terms but {len(c)} coefficients")
+        if not np.all(np.isfinite(c)):
+            raise CircuitError("a coefficient is not finite")
+        basis = list(basis)
+        if not 2 <= len(basis) <= 16:
+            raise CircuitError(f"{what}: the basis holds m + 1 states for 1 <= m <= 15, not {len(basis)}")
+        for b in basis:
+            self._partner(b, what)
+            if b.device != self.device:
+                raise CircuitError(f"{what}: a basis state lives on another device")
+        handles = [b._h.value for b in basis]
+        if self._h.value in handles:
+            raise CircuitError(f"{what}: the state itself is in the basis")
+        if len(set(handles)) != len(handles):
+            raise CircuitError(f"{what}: a state is in the basis twice")
+        pauli_sum_passes(self.n, terms)  # (malformed terms raise here)
+        return terms, c, basis, krylov_bar(len(basis) - 1, len(terms), float(np.sum(np.abs(c))), self.np_dtype)
+
+    def _lanczos(self, terms, c, basis, reorthogonalize: bool, bar: float):
+        """krylov_basis after the checks; also returns |self|"""
+        norm = float(np.sqrt(basis[0].linear_combination([self], [1.0], want_norm=True)))
+        if not (norm > 0.0 and np.isfinite(norm)):
+            raise CircuitError(f"the state's norm is {norm}")
+        basis[0].scale(1.0 / norm)
+        alphas, betas = [], []
+        for j in range(len(basis) - 1):
+            v, w = basis[j], basis[j + 1]
+            w.apply_pauli_sum(v, terms, c)
+            alpha = float(w.inner_products([v])[0].real)
+            if j == 0:
+                norm2 = w.linear_combination([w, v], [1.0, -alpha], want_norm=True)
+            else:
+                norm2 = w.linear_combination([w, v, basis[j - 1]], [1.0, -alpha, -betas[-1]], want_norm=True)
+            if reorthogonalize:
+                h = w.inner_products(basis[:j + 1])
+                norm2 = w.linear_combination([w] + basis[:j + 1], np.concatenate([[1.0], -h]), want_norm=True)
+            alphas.append(alpha)
+            betas.append(float(np.sqrt(norm2)))
+            if not betas[-1] > bar:  # an invariant subspace (or a NaN): basis[j + 1] is not a direction
+                break
+            w.scale(1.0 / betas[-1])
+        return np.array(alphas), np.array(betas), norm
+
+    def krylov_basis(self, terms, coeffs, basis, reorthogonalize: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+        """The Lanczos basis of `self` under H = sum_t coeffs[t] * terms[t] (real coefficients, the term forms of expect_pauli).
+        `basis` is a list of m + 1 distinct states (1 <= m <= 15) of the same n, precision and device, none of them `self`;
+        their content is overwritten, `self` is not changed.  Returns (alphas, betas), float64[k] each, k <= m the steps done.
+
+        basis[0] = self / |self|; step j: w = H v_j (apply_pauli_sum into basis[j + 1]), alphas[j] = Re <v_j|w>,
+        w <- w - alphas[j] v_j - betas[j-1] v_{j-1} in one linear_combination that also returns |w|^2; with `reorthogonalize`
+        h = inner_products(basis[:j + 1]) of w in one pass and w <- w - sum_i h_i v_i in one more combination;
+        betas[j] = |w|, basis[j + 1] = w / betas[j].  The tridiagonal matrix of alphas[:k] and betas[:k - 1] is H in the basis;
+        betas[k - 1] closes it.  The steps end early, with k < m, when betas[k - 1] <= krylov_bar(m, len(terms), sum |coeffs|,
+        dtype): the basis spans an invariant subspace and basis[k] is left unnormalised."""
+        terms, c, basis, bar = self._krylov_setup(terms, coeffs, basis, "krylov_basis")
+        return self._lanczos(terms, c, basis, bool(reorthogonalize), bar)[:2]
+
+    def ground_state(self, terms, coeffs, basis, restarts: int = 1) -> Tuple[float, float]:
+        """(energy, residual): the lowest Ritz pair of H = sum_t coeffs[t] * terms[t] from the Krylov space of `self`, restarted:
+        up to `restarts` rounds of krylov_basis (reorthogonalised), the tridiagonal matrix diagonalised on the host
+        (numpy.linalg.eigh), self <- sum_i y_i v_i for the lowest Ritz vector y in one combination, normalised.
+        residual = betas[k - 1] |y[k - 1]| = |H self - energy self| up to rounding; the rounds end early once it is at most
+        krylov_bar(...).  `basis` as for krylov_basis.  On return `self` holds the normalised Ritz vector of the last round."""
+        terms, c, basis, bar = self._krylov_setup(terms, coeffs, basis, "ground_state")
+        if int(restarts) < 1:
+            raise CircuitError("ground_state: at least one round")
+        energy = residual = float("nan")
+        for _ in range(int(restarts)):
+            alphas, betas, _ = self._lanczos(terms, c, basis, True, bar)
+            theta, y = tridiagonal_eigh(alphas, betas)
+            energy, residual = float(theta[0]), float(betas[-1] * abs(y[-1, 0]))
+            norm2 = self.linear_combination(basis[:len(alphas)], y[:, 0], want_norm=True)
+            self.scale(1.0 / np.sqrt(norm2))
+            if residual <= bar:
+                break
+        return energy, residual
+
+    def krylov_evolve(self, terms, coeffs, t: float, basis, substeps: int = 1) -> float:
+        """self <- exp(-i H t) self for H = sum_t coeffs[t] * terms[t] by `substeps` Krylov steps of tau = t / substeps: per step
+        krylov_basis (reorthogonalised), then self <- |self| sum_i [exp(-i T tau)]_{i0} v_i in one combination, T the
+        tridiagonal matrix, exponentiated on the host.  `basis` as for krylov_basis.  Returns the largest a-posteriori estimate
+        betas[k - 1] |tau| |[exp(-i T tau)]_{k-1,0}| |self| of a step's error over the steps."""
+        terms, c, basis, bar = self._krylov_setup(terms, coeffs, basis, "krylov_evolve")
+        if int(substeps) < 1 or not np.isfinite(float(t)):
+            raise CircuitError("krylov_evolve: a finite time and at least one step")
+        tau, worst = float(t) / int(substeps), 0.0
+        for _ in range(int(substeps)):
+            alphas, betas, norm = self._lanczos(terms, c, basis, True, bar)
+            column = tridiagonal_propagator_column(alphas, betas, tau)
+            worst = max(worst, float(betas[-1] * abs(tau) * abs(column[-1]) * norm))
+            self.linear_combination(basis[:len(alphas)], norm * column)
+        return worst
 
     def measure(self, indices: Sequence[int], measured: Optional[int] = None,
                 rand_u01: float = 0.0) -> Tuple[int, float]:
