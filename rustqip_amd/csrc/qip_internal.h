@@ -7,7 +7,9 @@
 //   qip_jit.hip       the run-time compiler behind qip_jit.h: hiprtc, disk cache, helper processes, resident kernels, plan memo
 //   qip_slice.hip     apply_op on device slices of any element type (qip_hip_apply_op_device): payload cache, kernels, routing
 //   qip_host.hip      host-pointer twins of the reference functions
-//   qip_measure.hip   measurement
+//   qip_measure.hip   measurement, sampling, reduced density matrices
+//   qip_pauli.hip     Pauli-string calls (expectation values, rotations, sums, matrix elements) and vector arithmetic of resident
+//                     states, over qip_pauli_plan.h (terms, planners, pass geometry: plain C++) and qip_pauli_kernels.h
 //   qip_dist.hip      the sharded state (planner, pack sweep, exchange)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -33,6 +35,7 @@
 #include "../../include/qip_hip.h"
 #include "../../include/qip_hip_debug.h"
 #include "qip_kernels.h"
+#include "qip_pauli_plan.h"  // the slot capacities the *_group options are held to (qip_core.hip)
 #include "qip_jit.h"
 
 using namespace qipk;

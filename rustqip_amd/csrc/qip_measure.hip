@@ -1,4 +1,4 @@
-// qip_measure.hip — measurement on the device (qip/src/state_ops/measurement_ops.rs).
+// qip_measure.hip — measurement on the device (qip/src/state_ops/measurement_ops.rs), batched sampling and reduced density matrices.
 #include "qip_internal.h"
 #include "../../include/qip_hipx.h"
 
@@ -557,603 +557,6 @@ extern "C" int qipx_state_soft_measure_many(qip_hip_state* s, const uint64_t* in
   if (!rand_u01 || !measured) return fail(QIP_ERR_INVALID, "null sample or result array");
   return s->dtype == QIP_C64 ? soft_measure_many_t<double>(s, md, rand_u01, count, measured)
                              : soft_measure_many_t<float>(s, md, rand_u01, count, measured);
-} QIP_CATCH_ALL
-
-// ---- expectation values of Pauli strings (include/qip_hipx.h) -----------------------------------------------------------
-//   reduce  every term to (x mask, z mask, n_Y mod 4) over amplitude-index bits (expect_reduce)
-//   plan    the terms sorted by x mask, stably, each run of one x cut into passes of at most `group` terms (expect_plan: also
-//           all that qipx_expect_pauli_passes runs)
-//   pass    one k_expect_pauli launch + one copy of its per-block partial sums; as many passes share a synchronise as their
-//           partial sums fit the scratch; the host adds a term's partial sums in block order and doubles the pair passes
-// The geometry of a pass (expect_geom) depends on n, the precision and the class of the x mask only (zero / bit 0 set / bit 0
-// clear), never on the group: together with the kernel's per-slot sums that makes a value a function of the state and its term.
-namespace {
-struct PauliTerm {
-  uint64_t x, z;
-  uint32_t ny;  // n_Y mod 4
-};
-struct ExpectPass {
-  uint32_t first, count;  // the terms order[first .. first + count), all of one x mask
-};
-struct ExpectGeom {
-  bool pair, packed;
-  uint64_t nwork, chunk;
-  uint32_t nblocks, shift, hbit;  // shift: 1 = positions in 16-byte elements of two amplitudes; hbit: x's highest bit, in elements
-};
-}  // namespace
-
-static int expect_reduce(uint32_t n, const uint64_t* term_start, const uint64_t* qubits, const uint8_t* paulis, uint64_t count,
-                         std::vector<PauliTerm>* terms) {
-  if (n > 63) return fail(QIP_ERR_INVALID, "expect_pauli: %u qubits", n);
-  if (!term_start || !qubits || !paulis) return fail(QIP_ERR_INVALID, "expect_pauli: null term array");
-  if (term_start[0] != 0) return fail(QIP_ERR_INVALID, "expect_pauli: term_start[0] is not 0");
-  terms->resize(count);
-  for (uint64_t t = 0; t < count; ++t) {
-    if (term_start[t + 1] < term_start[t]) return fail(QIP_ERR_INVALID, "expect_pauli: term_start decreases at term %llu", (unsigned long long)t);
-    PauliTerm pt{0, 0, 0};
-    uint64_t seen = 0;
-    for (uint64_t i = term_start[t]; i < term_start[t + 1]; ++i) {
-      if (qubits[i] >= n) return fail(QIP_ERR_INVALID, "expect_pauli: qubit %llu of term %llu out of range", (unsigned long long)qubits[i], (unsigned long long)t);
-      if (paulis[i] > 3) return fail(QIP_ERR_INVALID, "expect_pauli: Pauli code %u in term %llu", (unsigned)paulis[i], (unsigned long long)t);
-      const uint64_t bit = 1ull << (n - 1 - qubits[i]);
-      if (seen & bit) return fail(QIP_ERR_INVALID, "expect_pauli: qubit %llu repeated in term %llu", (unsigned long long)qubits[i], (unsigned long long)t);
-      seen |= bit;
-      if (paulis[i] == 1 || paulis[i] == 2) pt.x |= bit;
-      if (paulis[i] == 2 || paulis[i] == 3) pt.z |= bit;
-      if (paulis[i] == 2) pt.ny = (pt.ny + 1) & 3u;
-    }
-    (*terms)[t] = pt;
-  }
-  return QIP_OK;
-}
-
-static void expect_plan(const std::vector<PauliTerm>& terms, uint32_t group, std::vector<uint32_t>* order, std::vector<ExpectPass>* passes) {
-  order->resize(terms.size());
-  for (size_t t = 0; t < terms.size(); ++t) (*order)[t] = (uint32_t)t;
-  std::stable_sort(order->begin(), order->end(), [&](uint32_t a, uint32_t b) { return terms[a].x < terms[b].x; });
-  passes->clear();
-  for (size_t at = 0; at < order->size();) {
-    size_t end = at;
-    while (end < order->size() && terms[(*order)[end]].x == terms[(*order)[at]].x) ++end;
-    for (; at < end; at += std::min<size_t>(group, end - at))
-      passes->push_back(ExpectPass{(uint32_t)at, (uint32_t)std::min<size_t>(group, end - at)});
-  }
-}
-
-extern "C" int qipx_expect_pauli_passes(uint32_t n, const uint64_t* term_start, const uint64_t* qubits, const uint8_t* paulis,
-                                        uint64_t count, uint32_t group, uint64_t* passes) try {
-  if (!passes) return fail(QIP_ERR_INVALID, "null output");
-  if (group > (uint32_t)kExpectMaxGroup) return fail(QIP_ERR_INVALID, "expect_group is 1 to %d", kExpectMaxGroup);
-  *passes = 0;
-  if (count == 0) return QIP_OK;
-  if (count > 0xffffffffull) return fail(QIP_ERR_UNSUPPORTED, "expect_pauli: more than 2^32 - 1 terms");
-  std::vector<PauliTerm> terms;
-  QCHK(expect_reduce(n, term_start, qubits, paulis, count, &terms));
-  std::vector<uint32_t> order;
-  std::vector<ExpectPass> plan;
-  expect_plan(terms, group ? group : (uint32_t)kExpectGroupDefault, &order, &plan);
-  *passes = plan.size();
-  return QIP_OK;
-} QIP_CATCH_ALL
-
-static uint32_t top_bit(uint64_t v) {
-  uint32_t b = 0;
-  while (v >>= 1) ++b;
-  return b;
-}
-
-template <typename T>
-static ExpectGeom expect_geom(const qip_hip_state* s, uint64_t x) {
-  ExpectGeom g;
-  g.pair = x != 0;
-  // Complex<f32>: 16-byte elements of two amplitudes unless the pair differs in index bit 0 (its halves would cross elements)
-  g.packed = std::is_same<T, float>::value && s->packed_f32 && s->n >= 2 && (x & 1ull) == 0;
-  g.shift = g.packed ? 1u : 0u;
-  g.hbit = g.pair ? top_bit(x) - g.shift : 0u;
-  g.nwork = (s->namps >> g.shift) >> (g.pair ? 1 : 0);
-  const uint64_t span = (uint64_t)(g.pair ? 2 : 4) << kStrideShift;  // one round of k_expect_pauli's main loop
-  g.chunk = std::min<uint64_t>(std::max<uint64_t>(g.nwork / 4096, span), g.nwork);
-  g.nblocks = (uint32_t)((g.nwork + g.chunk - 1) / g.chunk);
-  return g;
-}
-
-// slot `slot` of a pass's transposed z masks (k_expect_pauli's and k_pauli_rotate's `col` and `half`): bit `slot` of col[b] = the
-// amplitude-index bit behind work-index bit b lies under z
-static void pauli_columns(const ExpectGeom& g, uint32_t n, uint64_t z, uint32_t slot, uint32_t (&col)[64], uint32_t* half) {
-  if (g.packed && (z & 1ull)) *half |= 1u << slot;
-  for (uint32_t b = 0; b + g.shift + (g.pair ? 1 : 0) < n; ++b) {
-    const uint32_t pos = (g.pair && b >= g.hbit ? b + 1 : b) + g.shift;  // the amplitude-index bit behind work-index bit b
-    if ((z >> pos) & 1ull) col[b] |= 1u << slot;
-  }
-}
-
-template <typename T, int G>
-static void expect_launch_g(qip_hip_state* s, const ExpectGeom& g, const Ins& ins, const ExpectDesc& d, double* partial) {
-  const dim3 grid(g.nblocks), block(kBlock);
-  if (g.packed && g.pair)
-    hipLaunchKernelGGL((k_expect_pauli<float, G, true, f32x4>), grid, block, 0, s->stream, (const f32x4*)s->cur, g.nwork, g.chunk, ins, d, partial);
-  else if (g.packed)
-    hipLaunchKernelGGL((k_expect_pauli<float, G, false, f32x4>), grid, block, 0, s->stream, (const f32x4*)s->cur, g.nwork, g.chunk, ins, d, partial);
-  else if (g.pair)
-    hipLaunchKernelGGL((k_expect_pauli<T, G, true>), grid, block, 0, s->stream, (const amp_t<T>*)s->cur, g.nwork, g.chunk, ins, d, partial);
-  else
-    hipLaunchKernelGGL((k_expect_pauli<T, G, false>), grid, block, 0, s->stream, (const amp_t<T>*)s->cur, g.nwork, g.chunk, ins, d, partial);
-}
-
-// one pass: the terms `ids` (all of x mask `x`), partial sums to partial[slot * nblocks + block]
-template <typename T>
-static int expect_launch(qip_hip_state* s, const ExpectGeom& g, uint64_t x, const std::vector<PauliTerm>& terms, const uint32_t* ids,
-                         uint32_t count, double* partial) {
-  ExpectDesc d;
-  memset(&d, 0, sizeof d);
-  d.x = x >> g.shift;
-  d.count = count;
-  for (uint32_t slot = 0; slot < count; ++slot) {
-    const PauliTerm& t = terms[ids[slot]];
-    if (t.ny == 1 || t.ny == 2) d.flip |= 1u << slot;
-    if (t.ny & 1u) d.imag |= 1u << slot;
-    pauli_columns(g, s->n, t.z, slot, d.col, &d.half);
-  }
-  const Ins ins = g.pair ? make_ins({g.hbit}, 0) : make_ins({}, 0);
-  if (count <= 1) expect_launch_g<T, 1>(s, g, ins, d, partial);
-  else if (count <= 4) expect_launch_g<T, 4>(s, g, ins, d, partial);
-  else if (count <= 16) expect_launch_g<T, 16>(s, g, ins, d, partial);
-  else expect_launch_g<T, kExpectMaxGroup>(s, g, ins, d, partial);
-  HIPCHK(hipGetLastError());
-  return QIP_OK;
-}
-
-template <typename T>
-static int expect_pauli_t(qip_hip_state* s, const std::vector<PauliTerm>& terms, double* values) {
-  std::vector<uint32_t> order;
-  std::vector<ExpectPass> plan;
-  expect_plan(terms, (uint32_t)s->expect_group, &order, &plan);
-  std::vector<ExpectGeom> geom(plan.size());
-  size_t total = 0;
-  for (size_t p = 0; p < plan.size(); ++p) {
-    geom[p] = expect_geom<T>(s, terms[order[plan[p].first]].x);
-    total += (size_t)plan[p].count * geom[p].nblocks;
-  }
-  // the passes that share a synchronise: as many as keep their partial sums within 2^20 doubles (one pass needs <= 32 * 4096)
-  const size_t cap = std::min<size_t>(total, (size_t)1 << 20);
-  QCHK(ensure_partial(s, cap));
-  std::vector<double> part(cap);
-  for (size_t p = 0; p < plan.size();) {
-    size_t used = 0, q = p;
-    for (; q < plan.size(); ++q) {
-      const size_t need = (size_t)plan[q].count * geom[q].nblocks;
-      if (used + need > cap) break;
-      QCHK(expect_launch<T>(s, geom[q], terms[order[plan[q].first]].x, terms, order.data() + plan[q].first, plan[q].count, s->d_partial + used));
-      HIPCHK(hipMemcpyAsync(part.data() + used, s->d_partial + used, need * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-      used += need;
-    }
-    HIPCHK(hipStreamSynchronize(s->stream));
-    for (size_t at = 0; p < q; ++p) {
-      const uint32_t nb = geom[p].nblocks;
-      for (uint32_t slot = 0; slot < plan[p].count; ++slot, at += nb) {
-        double t = 0;
-        for (uint32_t b = 0; b < nb; ++b) t += part[at + b];
-        values[order[plan[p].first + slot]] = geom[p].pair ? 2.0 * t : t;
-      }
-    }
-  }
-  return QIP_OK;
-}
-
-extern "C" int qipx_state_expect_pauli(qip_hip_state* s, const uint64_t* term_start, const uint64_t* qubits, const uint8_t* paulis,
-                                       uint64_t count, double* values) try {
-  STATE_ENTER(s);
-  if (count == 0) return QIP_OK;
-  if (!values) return fail(QIP_ERR_INVALID, "expect_pauli: null result array");
-  if (count > 0xffffffffull) return fail(QIP_ERR_UNSUPPORTED, "expect_pauli: more than 2^32 - 1 terms");
-  std::vector<PauliTerm> terms;
-  QCHK(expect_reduce(s->n, term_start, qubits, paulis, count, &terms));
-  return s->dtype == QIP_C64 ? expect_pauli_t<double>(s, terms, values) : expect_pauli_t<float>(s, terms, values);
-} QIP_CATCH_ALL
-
-// ---- Pauli-string rotations exp(-i theta P) in place (include/qip_hipx.h) ------------------------------------------------
-//   reduce  as above (expect_reduce), plus the angles: finite, cos and sin in double
-//   plan    maximal runs of CONSECUTIVE terms of one x mask, cut at `group` terms (rotate_plan: also all that
-//           qipx_pauli_rotation_passes runs); the terms keep their order, they do not commute in general
-//   pass    one k_pauli_rotate launch in the geometry of the expect pass of that x mask (expect_geom), queued on the stream
-// Everything is checked before the first launch; nothing is waited for.
-static void rotate_plan(const std::vector<PauliTerm>& terms, uint32_t group, std::vector<ExpectPass>* passes) {
-  passes->clear();
-  for (size_t at = 0; at < terms.size();) {
-    size_t end = at + 1;
-    while (end < terms.size() && end - at < group && terms[end].x == terms[at].x) ++end;
-    passes->push_back(ExpectPass{(uint32_t)at, (uint32_t)(end - at)});
-    at = end;
-  }
-}
-
-extern "C" int qipx_pauli_rotation_passes(uint32_t n, const uint64_t* term_start, const uint64_t* qubits, const uint8_t* paulis,
-                                          uint64_t count, uint32_t group, uint64_t* passes) try {
-  if (!passes) return fail(QIP_ERR_INVALID, "null output");
-  if (group > (uint32_t)kRotateMaxGroup) return fail(QIP_ERR_INVALID, "rotate_group is 1 to %d", kRotateMaxGroup);
-  *passes = 0;
-  if (count == 0) return QIP_OK;
-  if (count > 0xffffffffull) return fail(QIP_ERR_UNSUPPORTED, "pauli_rotations: more than 2^32 - 1 terms");
-  std::vector<PauliTerm> terms;
-  QCHK(expect_reduce(n, term_start, qubits, paulis, count, &terms));
-  std::vector<ExpectPass> plan;
-  rotate_plan(terms, group ? group : (uint32_t)kRotateGroupDefault, &plan);
-  *passes = plan.size();
-  return QIP_OK;
-} QIP_CATCH_ALL
-
-template <typename T, int G>
-static void rotate_launch_g(qip_hip_state* s, const ExpectGeom& g, const Ins& ins, const RotateDesc<T>& d) {
-  const dim3 grid(g.nblocks), block(kBlock);
-  if constexpr (std::is_same<T, float>::value) {
-    if (g.packed) {
-      if (g.pair) hipLaunchKernelGGL((k_pauli_rotate<float, G, true, f32x4>), grid, block, 0, s->stream, (f32x4*)s->cur, g.nwork, g.chunk, ins, d);
-      else hipLaunchKernelGGL((k_pauli_rotate<float, G, false, f32x4>), grid, block, 0, s->stream, (f32x4*)s->cur, g.nwork, g.chunk, ins, d);
-      return;
-    }
-  }
-  if (g.pair) hipLaunchKernelGGL((k_pauli_rotate<T, G, true>), grid, block, 0, s->stream, (amp_t<T>*)s->cur, g.nwork, g.chunk, ins, d);
-  else hipLaunchKernelGGL((k_pauli_rotate<T, G, false>), grid, block, 0, s->stream, (amp_t<T>*)s->cur, g.nwork, g.chunk, ins, d);
-}
-
-template <typename T>
-static int rotate_t(qip_hip_state* s, const std::vector<PauliTerm>& terms, const double* angles) {
-  std::vector<ExpectPass> plan;
-  rotate_plan(terms, (uint32_t)s->rotate_group, &plan);
-  for (const ExpectPass& pass : plan) {
-    const uint64_t x = terms[pass.first].x;
-    const ExpectGeom g = expect_geom<T>(s, x);
-    RotateDesc<T> d;
-    memset(&d, 0, sizeof d);
-    d.x = x >> g.shift;
-    d.count = pass.count;
-    for (uint32_t slot = 0; slot < pass.count; ++slot) {
-      const PauliTerm& t = terms[pass.first + slot];
-      const uint32_t p = (t.ny + 3u) & 3u;  // -i i^n_Y = i^p
-      if (p & 1u) d.swap |= 1u << slot;
-      if (p & 2u) d.hi |= 1u << slot;
-      if (t.ny & 1u) d.odd |= 1u << slot;
-      pauli_columns(g, s->n, t.z, slot, d.col, &d.half);
-      d.c[slot] = (T)cos(angles[pass.first + slot]);  // in double, rounded once to the state's precision
-      d.s[slot] = (T)sin(angles[pass.first + slot]);
-    }
-    const Ins ins = g.pair ? make_ins({g.hbit}, 0) : make_ins({}, 0);
-    if (pass.count <= 1) rotate_launch_g<T, 1>(s, g, ins, d);
-    else if (pass.count <= 4) rotate_launch_g<T, 4>(s, g, ins, d);
-    else rotate_launch_g<T, kRotateMaxGroup>(s, g, ins, d);  // (a loop over the slots in use: one kernel for 5 to 32 terms)
-    HIPCHK(hipGetLastError());
-  }
-  return QIP_OK;
-}
-
-extern "C" int qipx_state_apply_pauli_rotations(qip_hip_state* s, const uint64_t* term_start, const uint64_t* qubits,
-                                                const uint8_t* paulis, const double* angles, uint64_t count) try {
-  STATE_ENTER_RAW(s);
-  if (count == 0) return QIP_OK;
-  if (!angles) return fail(QIP_ERR_INVALID, "pauli_rotations: null angle array");
-  if (count > 0xffffffffull) return fail(QIP_ERR_UNSUPPORTED, "pauli_rotations: more than 2^32 - 1 terms");
-  std::vector<PauliTerm> terms;
-  QCHK(expect_reduce(s->n, term_start, qubits, paulis, count, &terms));
-  for (uint64_t t = 0; t < count; ++t)
-    if (!std::isfinite(angles[t])) return fail(QIP_ERR_INVALID, "pauli_rotations: the angle of term %llu is not finite", (unsigned long long)t);
-  if (!s->layout.empty()) QCHK(state_settle(s));  // (a relabelled state: the caller's order first, as by STATE_ENTER)
-  return s->dtype == QIP_C64 ? rotate_t<double>(s, terms, angles) : rotate_t<float>(s, terms, angles);
-} QIP_CATCH_ALL
-
-// ---- two states and Pauli strings: dst (+)= (sum_t c_t P_t) src and <bra| P_t |ket> (include/qip_hipx.h) ---------------------
-//   meet    the two handles as copy_from and max_abs_diff meet theirs (pair_meet: the checks; pair_settle: the caller's order and
-//           the other handle's stream drained), everything that can refuse the call before anything is queued
-//   reduce  as above (expect_reduce)
-//   plan    expect_plan: sorted stably by x mask, each run cut at `group` terms (also all that qipx_pauli_sum_passes runs)
-//   pass    one k_pauli_sum / k_pauli_melem launch in the geometry of the expect pass of that x mask (expect_geom)
-// Both calls are complete when they return.
-static int pair_meet(const char* what, qip_hip_state* own, qip_hip_state* other) {
-  if (!other) return fail(QIP_ERR_INVALID, "%s: null state handle", what);
-  if (other->poisoned) return fail(QIP_ERR_DEVICE, "%s: the other state is unusable: %s", what, other->poison_msg.c_str());
-  if (own->n != other->n || own->dtype != other->dtype) return fail(QIP_ERR_INVALID, "%s: states differ in size or precision", what);
-  if (own->device != other->device) return fail(QIP_ERR_UNSUPPORTED, "%s: states live on different devices", what);
-  return QIP_OK;
-}
-
-// both in the caller's order, and everything queued on `other` has landed: the work then runs on `own`'s stream
-static int pair_settle(qip_hip_state* own, qip_hip_state* other) {
-  if (!own->layout.empty()) QCHK(state_settle(own));
-  if (other != own) {
-    if (!other->layout.empty()) QCHK(state_settle(other));
-    HIPCHK(hipStreamSynchronize(other->stream));
-  }
-  return QIP_OK;
-}
-
-extern "C" int qipx_pauli_sum_passes(uint32_t n, const uint64_t* term_start, const uint64_t* qubits, const uint8_t* paulis,
-                                     uint64_t count, uint32_t group, uint64_t* passes) try {
-  if (!passes) return fail(QIP_ERR_INVALID, "null output");
-  if (group > (uint32_t)kSumMaxGroup) return fail(QIP_ERR_INVALID, "sum_group is 1 to %d", kSumMaxGroup);
-  *passes = 0;
-  if (count == 0) return QIP_OK;
-  if (count > 0xffffffffull) return fail(QIP_ERR_UNSUPPORTED, "pauli_sum: more than 2^32 - 1 terms");
-  std::vector<PauliTerm> terms;
-  QCHK(expect_reduce(n, term_start, qubits, paulis, count, &terms));
-  std::vector<uint32_t> order;
-  std::vector<ExpectPass> plan;
-  expect_plan(terms, group ? group : (uint32_t)kSumGroupDefault, &order, &plan);
-  *passes = plan.size();
-  return QIP_OK;
-} QIP_CATCH_ALL
-
-template <typename T, int G, bool FIRST>
-static void sum_launch_g(qip_hip_state* dst, const qip_hip_state* src, const ExpectGeom& g, const Ins& ins, const SumDesc<T>& d) {
-  const dim3 grid(g.nblocks), block(kBlock);
-  if constexpr (std::is_same<T, float>::value) {
-    if (g.packed) {
-      if (g.pair) hipLaunchKernelGGL((k_pauli_sum<float, G, true, FIRST, f32x4>), grid, block, 0, dst->stream, (f32x4*)dst->cur, (const f32x4*)src->cur, g.nwork, g.chunk, ins, d);
-      else hipLaunchKernelGGL((k_pauli_sum<float, G, false, FIRST, f32x4>), grid, block, 0, dst->stream, (f32x4*)dst->cur, (const f32x4*)src->cur, g.nwork, g.chunk, ins, d);
-      return;
-    }
-  }
-  if (g.pair) hipLaunchKernelGGL((k_pauli_sum<T, G, true, FIRST>), grid, block, 0, dst->stream, (amp_t<T>*)dst->cur, (const amp_t<T>*)src->cur, g.nwork, g.chunk, ins, d);
-  else hipLaunchKernelGGL((k_pauli_sum<T, G, false, FIRST>), grid, block, 0, dst->stream, (amp_t<T>*)dst->cur, (const amp_t<T>*)src->cur, g.nwork, g.chunk, ins, d);
-}
-
-template <typename T, bool FIRST>
-static void sum_launch(qip_hip_state* dst, const qip_hip_state* src, const ExpectGeom& g, const Ins& ins, const SumDesc<T>& d) {
-  if (d.count <= 1) sum_launch_g<T, 1, FIRST>(dst, src, g, ins, d);
-  else if (d.count <= 4) sum_launch_g<T, 4, FIRST>(dst, src, g, ins, d);
-  else sum_launch_g<T, kSumMaxGroup, FIRST>(dst, src, g, ins, d);  // (a loop over the slots in use: one kernel for 5 to 32 terms)
-}
-
-template <typename T>
-static int pauli_sum_t(qip_hip_state* dst, const qip_hip_state* src, const std::vector<PauliTerm>& terms, const double* coeffs,
-                       bool accumulate) {
-  std::vector<uint32_t> order;
-  std::vector<ExpectPass> plan;
-  expect_plan(terms, (uint32_t)dst->sum_group, &order, &plan);
-  if (plan.empty() && !accumulate) HIPCHK(hipMemsetAsync(dst->cur, 0, dst->namps * dst->amp_bytes, dst->stream));
-  bool first = !accumulate;
-  for (const ExpectPass& pass : plan) {
-    const uint64_t x = terms[order[pass.first]].x;
-    const ExpectGeom g = expect_geom<T>(dst, x);
-    SumDesc<T> d;
-    memset(&d, 0, sizeof d);
-    d.x = x >> g.shift;
-    d.count = pass.count;
-    for (uint32_t slot = 0; slot < pass.count; ++slot) {
-      const uint32_t id = order[pass.first + slot];
-      const PauliTerm& t = terms[id];
-      if (t.ny & 1u) d.odd |= 1u << slot;
-      pauli_columns(g, dst->n, t.z, slot, d.col, &d.half);
-      const double cr = coeffs[2 * (size_t)id], ci = coeffs[2 * (size_t)id + 1];
-      // k = c i^n_Y: a swap and sign flips in double, then rounded once to the state's precision
-      d.kr[slot] = (T)(t.ny == 0 ? cr : t.ny == 1 ? -ci : t.ny == 2 ? -cr : ci);
-      d.ki[slot] = (T)(t.ny == 0 ? ci : t.ny == 1 ? cr : t.ny == 2 ? -ci : -cr);
-    }
-    const Ins ins = g.pair ? make_ins({g.hbit}, 0) : make_ins({}, 0);
-    if (first) sum_launch<T, true>(dst, src, g, ins, d);
-    else sum_launch<T, false>(dst, src, g, ins, d);
-    HIPCHK(hipGetLastError());
-    first = false;
-  }
-  HIPCHK(hipStreamSynchronize(dst->stream));  // complete on return: the caller may touch `src` at once
-  return QIP_OK;
-}
-
-extern "C" int qipx_state_apply_pauli_sum(qip_hip_state* dst, qip_hip_state* src, const uint64_t* term_start, const uint64_t* qubits,
-                                          const uint8_t* paulis, const double* coeffs, uint64_t count, int accumulate) try {
-  STATE_ENTER_RAW(dst);
-  QCHK(pair_meet("pauli_sum", dst, src));
-  if (dst == src) return fail(QIP_ERR_INVALID, "pauli_sum: the destination is the source (later passes need the source intact)");
-  std::vector<PauliTerm> terms;
-  if (count > 0) {
-    if (!coeffs) return fail(QIP_ERR_INVALID, "pauli_sum: null coefficient array");
-    if (count > 0xffffffffull) return fail(QIP_ERR_UNSUPPORTED, "pauli_sum: more than 2^32 - 1 terms");
-    QCHK(expect_reduce(dst->n, term_start, qubits, paulis, count, &terms));
-    for (uint64_t t = 0; t < count; ++t)
-      if (!std::isfinite(coeffs[2 * t]) || !std::isfinite(coeffs[2 * t + 1]))
-        return fail(QIP_ERR_INVALID, "pauli_sum: the coefficient of term %llu is not finite", (unsigned long long)t);
-  }
-  QCHK(pair_settle(dst, src));
-  return dst->dtype == QIP_C64 ? pauli_sum_t<double>(dst, src, terms, coeffs, accumulate != 0)
-                               : pauli_sum_t<float>(dst, src, terms, coeffs, accumulate != 0);
-} QIP_CATCH_ALL
-
-template <typename T, int G>
-static void melem_launch_g(qip_hip_state* ket, const qip_hip_state* bra, const ExpectGeom& g, const Ins& ins, const MelemDesc& d,
-                           double* partial) {
-  const dim3 grid(g.nblocks), block(kBlock);
-  if (g.packed && g.pair)
-    hipLaunchKernelGGL((k_pauli_melem<float, G, true, f32x4>), grid, block, 0, ket->stream, (const f32x4*)bra->cur, (const f32x4*)ket->cur, g.nwork, g.chunk, ins, d, partial);
-  else if (g.packed)
-    hipLaunchKernelGGL((k_pauli_melem<float, G, false, f32x4>), grid, block, 0, ket->stream, (const f32x4*)bra->cur, (const f32x4*)ket->cur, g.nwork, g.chunk, ins, d, partial);
-  else if (g.pair)
-    hipLaunchKernelGGL((k_pauli_melem<T, G, true>), grid, block, 0, ket->stream, (const amp_t<T>*)bra->cur, (const amp_t<T>*)ket->cur, g.nwork, g.chunk, ins, d, partial);
-  else
-    hipLaunchKernelGGL((k_pauli_melem<T, G, false>), grid, block, 0, ket->stream, (const amp_t<T>*)bra->cur, (const amp_t<T>*)ket->cur, g.nwork, g.chunk, ins, d, partial);
-}
-
-template <typename T>
-static int pauli_melem_t(qip_hip_state* ket, const qip_hip_state* bra, const std::vector<PauliTerm>& terms, double* values) {
-  std::vector<uint32_t> order;
-  std::vector<ExpectPass> plan;
-  expect_plan(terms, (uint32_t)std::min<int64_t>(ket->expect_group, kMelemMaxGroup), &order, &plan);
-  std::vector<ExpectGeom> geom(plan.size());
-  size_t total = 0;
-  for (size_t p = 0; p < plan.size(); ++p) {
-    geom[p] = expect_geom<T>(ket, terms[order[plan[p].first]].x);
-    total += 2 * (size_t)plan[p].count * geom[p].nblocks;
-  }
-  // the passes that share a synchronise: as in expect_pauli_t (one pass needs <= 2 * 16 * 4096 doubles)
-  const size_t cap = std::min<size_t>(total, (size_t)1 << 20);
-  QCHK(ensure_partial(ket, cap));
-  std::vector<double> part(cap);
-  for (size_t p = 0; p < plan.size();) {
-    size_t used = 0, q = p;
-    for (; q < plan.size(); ++q) {
-      const size_t need = 2 * (size_t)plan[q].count * geom[q].nblocks;
-      if (used + need > cap) break;
-      const ExpectGeom& g = geom[q];
-      MelemDesc d;
-      memset(&d, 0, sizeof d);
-      d.x = terms[order[plan[q].first]].x >> g.shift;
-      d.count = plan[q].count;
-      for (uint32_t slot = 0; slot < d.count; ++slot) {
-        const PauliTerm& t = terms[order[plan[q].first + slot]];
-        if (t.ny & 1u) d.odd |= 1u << slot;
-        pauli_columns(g, ket->n, t.z, slot, d.col, &d.half);
-      }
-      const Ins ins = g.pair ? make_ins({g.hbit}, 0) : make_ins({}, 0);
-      if (d.count <= 1) melem_launch_g<T, 1>(ket, bra, g, ins, d, ket->d_partial + used);
-      else if (d.count <= 4) melem_launch_g<T, 4>(ket, bra, g, ins, d, ket->d_partial + used);
-      else melem_launch_g<T, kMelemMaxGroup>(ket, bra, g, ins, d, ket->d_partial + used);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(part.data() + used, ket->d_partial + used, need * sizeof(double), hipMemcpyDeviceToHost, ket->stream));
-      used += need;
-    }
-    HIPCHK(hipStreamSynchronize(ket->stream));
-    for (size_t at = 0; p < q; ++p) {
-      const uint32_t nb = geom[p].nblocks;
-      for (uint32_t slot = 0; slot < plan[p].count; ++slot, at += 2 * (size_t)nb) {
-        double re = 0, im = 0;
-        for (uint32_t b = 0; b < nb; ++b) re += part[at + b], im += part[at + nb + b];
-        const uint32_t id = order[plan[p].first + slot], ny = terms[id].ny;  // times i^n_Y: exact
-        values[2 * (size_t)id] = ny == 0 ? re : ny == 1 ? -im : ny == 2 ? -re : im;
-        values[2 * (size_t)id + 1] = ny == 0 ? im : ny == 1 ? re : ny == 2 ? -im : -re;
-      }
-    }
-  }
-  return QIP_OK;
-}
-
-extern "C" int qipx_state_pauli_matrix_elements(qip_hip_state* bra, qip_hip_state* ket, const uint64_t* term_start,
-                                                const uint64_t* qubits, const uint8_t* paulis, uint64_t count, double* values) try {
-  STATE_ENTER_RAW(ket);
-  QCHK(pair_meet("pauli_matrix_elements", ket, bra));
-  if (count == 0) return QIP_OK;
-  if (!values) return fail(QIP_ERR_INVALID, "pauli_matrix_elements: null result array");
-  if (count > 0xffffffffull) return fail(QIP_ERR_UNSUPPORTED, "pauli_matrix_elements: more than 2^32 - 1 terms");
-  std::vector<PauliTerm> terms;
-  QCHK(expect_reduce(ket->n, term_start, qubits, paulis, count, &terms));
-  QCHK(pair_settle(ket, bra));
-  return ket->dtype == QIP_C64 ? pauli_melem_t<double>(ket, bra, terms, values) : pauli_melem_t<float>(ket, bra, terms, values);
-} QIP_CATCH_ALL
-
-// ---- vector arithmetic of resident states: dst <- sum_i c_i src_i and <bra_i|ket> (include/qip_hipx.h) -------------------
-//   meet    every handle as the two-state calls above meet theirs (pair_meet, pair_settle), all refusals before anything is queued
-//   launch  ONE k_lincomb / k_inner_many launch in a grid that depends on the number of 16-byte elements only (vec_grid), in the
-//           smallest capacity of kVecCaps that holds the call
-//   fold    per-block partials in the own state's reduction scratch, added on the host in block order
-// Both calls are complete when they return.
-static unsigned vec_grid(uint64_t nelems) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>(nelems / (kBlock * 4), 1), 4096); }
-// 16-byte elements of a state: one Complex<f64>, two Complex<f32> (n >= 1: never half an element)
-static uint64_t vec_elems(const qip_hip_state* s) { return s->dtype == QIP_C64 ? s->namps : s->namps / 2; }
-
-template <typename T, int G, bool NORM>
-static void lincomb_launch_g(qip_hip_state* dst, const LincombDesc<T>& d, unsigned gx, uint64_t nelems) {
-  using E = typename std::conditional<std::is_same<T, float>::value, f32x4, amp_t<T>>::type;
-  hipLaunchKernelGGL((k_lincomb<T, G, NORM, E>), dim3(gx), dim3(kBlock), 0, dst->stream, (E*)dst->cur, nelems, d, dst->d_partial);
-}
-
-template <typename T, bool NORM>
-static void lincomb_launch(qip_hip_state* dst, const LincombDesc<T>& d, unsigned gx, uint64_t nelems) {
-  // the capacities: 1 to 4 sources each have their own (scale, axpy, the Lanczos update of three), then 8 and 16
-  if (d.count <= 1) lincomb_launch_g<T, 1, NORM>(dst, d, gx, nelems);
-  else if (d.count == 2) lincomb_launch_g<T, 2, NORM>(dst, d, gx, nelems);
-  else if (d.count == 3) lincomb_launch_g<T, 3, NORM>(dst, d, gx, nelems);
-  else if (d.count == 4) lincomb_launch_g<T, 4, NORM>(dst, d, gx, nelems);
-  else if (d.count <= 8) lincomb_launch_g<T, 8, NORM>(dst, d, gx, nelems);
-  else lincomb_launch_g<T, kVecMax, NORM>(dst, d, gx, nelems);
-}
-
-template <typename T>
-static int lincomb_t(qip_hip_state* dst, qip_hip_state* const* srcs, const double* coeffs, uint32_t count, double* norm_sqr) {
-  const uint64_t nelems = vec_elems(dst);
-  const unsigned gx = vec_grid(nelems);
-  LincombDesc<T> d;
-  memset(&d, 0, sizeof d);
-  d.count = count;
-  for (uint32_t i = 0; i < count; ++i) {
-    d.src[i] = srcs[i]->cur;
-    d.cr[i] = (T)coeffs[2 * (size_t)i];
-    d.ci[i] = (T)coeffs[2 * (size_t)i + 1];
-  }
-  if (norm_sqr) {
-    QCHK(ensure_partial(dst, gx));
-    lincomb_launch<T, true>(dst, d, gx, nelems);
-  } else {
-    lincomb_launch<T, false>(dst, d, gx, nelems);
-  }
-  HIPCHK(hipGetLastError());
-  std::vector<double> part(norm_sqr ? gx : 0);
-  if (norm_sqr) HIPCHK(hipMemcpyAsync(part.data(), dst->d_partial, gx * sizeof(double), hipMemcpyDeviceToHost, dst->stream));
-  HIPCHK(hipStreamSynchronize(dst->stream));  // complete on return: the caller may change a source at once
-  if (norm_sqr) {
-    double t = 0;
-    for (double v : part) t += v;
-    *norm_sqr = t;
-  }
-  return QIP_OK;
-}
-
-extern "C" int qipx_state_linear_combination(qip_hip_state* dst, qip_hip_state* const* srcs, const double* coeffs, uint32_t count,
-                                             double* norm_sqr) try {
-  STATE_ENTER_RAW(dst);
-  if (count > (uint32_t)kVecMax) return fail(QIP_ERR_UNSUPPORTED, "linear_combination: %u sources, at most %d are supported", count, kVecMax);
-  if (count > 0 && (!srcs || !coeffs)) return fail(QIP_ERR_INVALID, "linear_combination: null source or coefficient array");
-  for (uint32_t i = 0; i < count; ++i) QCHK(pair_meet("linear_combination", dst, srcs[i]));
-  for (uint32_t i = 0; i < count; ++i)
-    if (!std::isfinite(coeffs[2 * (size_t)i]) || !std::isfinite(coeffs[2 * (size_t)i + 1]))
-      return fail(QIP_ERR_INVALID, "linear_combination: the coefficient of source %u is not finite", i);
-  QCHK(pair_settle(dst, dst));
-  for (uint32_t i = 0; i < count; ++i) QCHK(pair_settle(dst, srcs[i]));
-  if (count == 0) {
-    HIPCHK(hipMemsetAsync(dst->cur, 0, dst->namps * dst->amp_bytes, dst->stream));
-    HIPCHK(hipStreamSynchronize(dst->stream));
-    if (norm_sqr) *norm_sqr = 0.0;
-    return QIP_OK;
-  }
-  return dst->dtype == QIP_C64 ? lincomb_t<double>(dst, srcs, coeffs, count, norm_sqr) : lincomb_t<float>(dst, srcs, coeffs, count, norm_sqr);
-} QIP_CATCH_ALL
-
-template <typename T, int G>
-static void inner_launch_g(qip_hip_state* ket, const InnerDesc& d, unsigned gx, uint64_t nelems) {
-  using E = typename std::conditional<std::is_same<T, float>::value, f32x4, amp_t<T>>::type;
-  hipLaunchKernelGGL((k_inner_many<T, G, E>), dim3(gx), dim3(kBlock), 0, ket->stream, (const E*)ket->cur, nelems, d, ket->d_partial);
-}
-
-template <typename T>
-static int inner_many_t(qip_hip_state* ket, qip_hip_state* const* bras, uint32_t count, double* values) {
-  const uint64_t nelems = vec_elems(ket);
-  const unsigned gx = vec_grid(nelems);
-  InnerDesc d;
-  memset(&d, 0, sizeof d);
-  d.count = count;
-  for (uint32_t i = 0; i < count; ++i) d.bra[i] = bras[i]->cur;
-  const size_t need = 2 * (size_t)count * gx;
-  QCHK(ensure_partial(ket, need));
-  if (count <= 1) inner_launch_g<T, 1>(ket, d, gx, nelems);
-  else if (count <= 2) inner_launch_g<T, 2>(ket, d, gx, nelems);
-  else if (count <= 4) inner_launch_g<T, 4>(ket, d, gx, nelems);
-  else if (count <= 8) inner_launch_g<T, 8>(ket, d, gx, nelems);
-  else inner_launch_g<T, kVecMax>(ket, d, gx, nelems);
-  HIPCHK(hipGetLastError());
-  std::vector<double> part(need);
-  HIPCHK(hipMemcpyAsync(part.data(), ket->d_partial, need * sizeof(double), hipMemcpyDeviceToHost, ket->stream));
-  HIPCHK(hipStreamSynchronize(ket->stream));
-  for (uint32_t i = 0; i < count; ++i) {
-    double re = 0, im = 0;
-    for (unsigned b = 0; b < gx; ++b) re += part[(size_t)(2 * i) * gx + b], im += part[(size_t)(2 * i + 1) * gx + b];
-    values[2 * (size_t)i] = re, values[2 * (size_t)i + 1] = im;
-  }
-  return QIP_OK;
-}
-
-extern "C" int qipx_state_inner_products(qip_hip_state* const* bras, uint32_t count, qip_hip_state* ket, double* values) try {
-  STATE_ENTER_RAW(ket);
-  if (count == 0) return QIP_OK;
-  if (count > (uint32_t)kVecMax) return fail(QIP_ERR_UNSUPPORTED, "inner_products: %u bras, at most %d are supported", count, kVecMax);
-  if (!bras || !values) return fail(QIP_ERR_INVALID, "inner_products: null bra or result array");
-  for (uint32_t i = 0; i < count; ++i) QCHK(pair_meet("inner_products", ket, bras[i]));
-  for (uint32_t i = 0; i < count; ++i) QCHK(pair_settle(ket, bras[i]));
-  return ket->dtype == QIP_C64 ? inner_many_t<double>(ket, bras, count, values) : inner_many_t<float>(ket, bras, count, values);
 } QIP_CATCH_ALL
 
 // ---- reduced density matrices (include/qip_hipx.h) ----------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """Expectation values of Pauli strings on a device state (include/qip_hipx.h: qipx_state_expect_pauli, HipState.expect_pauli):
 k_expect_pauli's single-amplitude (x = 0) and pair passes, plain and packed Complex<f32> elements, the grouping into passes and
-the scatter back into input order (rustqip_amd/csrc/qip_measure.hip).
+the scatter back into input order (rustqip_amd/csrc/qip_pauli.hip).
 
 The bar of every comparison with the reference (tests/expect_pauli_ref.py: double products, math.fsum) is
 

@@ -1,6 +1,6 @@
 """Pauli-string rotations exp(-i theta P) on a device state (include/qip_hipx.h: qipx_state_apply_pauli_rotations,
 HipState.apply_pauli_rotations / evolve): k_pauli_rotate's single-amplitude (x = 0) and pair passes, plain and packed
-Complex<f32> elements, every slot capacity, the grouping of consecutive terms into passes (rustqip_amd/csrc/qip_measure.hip).
+Complex<f32> elements, every slot capacity, the grouping of consecutive terms into passes (rustqip_amd/csrc/qip_pauli.hip).
 
 The reference and the two bars are those of tests/pauli_rotation_ref.py, with u = 2^-53 (Complex<f64>) or 2^-24 (Complex<f32>):
 

@@ -129,8 +129,10 @@ def test_refuses_what_expect_pauli_passes_refuses():
         for bad in MALFORMED:
             assert _raw(exp, 4, *bad, 2, group)[0] == _ffi.QIP_ERR_INVALID
             message = _ffi.last_error()
+            assert message.startswith("expect_pauli: ")
             assert _raw(fn, 4, *bad, 2, group)[0] == _ffi.QIP_ERR_INVALID
-            assert _ffi.last_error() == message  # the same check, the same message
+            # the same check, the same text, under the name of the call it came from
+            assert _ffi.last_error() == "pauli_sum: " + message[len("expect_pauli: "):]
         assert _raw(fn, 4, [0], [], [], 0, group, null=(0, 1, 2)) == (_ffi.QIP_OK, 0)  # no terms: null arrays allowed
     assert _raw(fn, 4, *ok, 2, 33)[0] == _ffi.QIP_ERR_INVALID
     assert _raw(fn, 4, *ok, 2, 32) == (_ffi.QIP_OK, 2)

@@ -81,8 +81,10 @@ def test_refuses_what_expect_pauli_passes_refuses():
         for bad in MALFORMED:
             assert _raw(exp, 4, *bad, 2, group)[0] == _ffi.QIP_ERR_INVALID
             message = _ffi.last_error()
+            assert message.startswith("expect_pauli: ")
             assert _raw(rot, 4, *bad, 2, group)[0] == _ffi.QIP_ERR_INVALID
-            assert _ffi.last_error() == message  # the same check, the same message
+            # the same check, the same text, under the name of the call it came from
+            assert _ffi.last_error() == "pauli_rotations: " + message[len("expect_pauli: "):]
         assert _raw(rot, 4, [0, 2, 3], [0, 3, 0], [1, 3, 2], 2, group) == (_ffi.QIP_OK, 2 if group else 1)  # the same qubit in two terms is fine
         assert _raw(rot, 4, [0], [], [], 0, group, null=(0, 1, 2)) == (_ffi.QIP_OK, 0)  # no terms: null arrays allowed
     assert _raw(rot, 4, *ok, 2, 33)[0] == _ffi.QIP_ERR_INVALID

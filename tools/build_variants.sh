@@ -10,7 +10,7 @@ while [ $# -ge 2 ]; do
   tag=$1; defs=$2; shift 2
   ( /opt/rocm/bin/hipcc $F $U $defs -c csrc/qip_tile_interp.hip -o build/qip_tile_interp_v$tag.o &&
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -Wl,--version-script=csrc/exports.map -o lib/libqip_hip_v$tag.so \
-      build/qip_core.o build/qip_launch.o build/qip_tile_sched.o build/qip_circuit.o build/qip_tile_interp_v$tag.o build/qip_jit.o build/qip_slice.o build/qip_host.o build/qip_measure.o build/qip_dist.o -ldl ) &
+      build/qip_core.o build/qip_launch.o build/qip_tile_sched.o build/qip_circuit.o build/qip_tile_interp_v$tag.o build/qip_jit.o build/qip_slice.o build/qip_host.o build/qip_measure.o build/qip_pauli.o build/qip_dist.o -ldl ) &
 done
 wait
 ls -la lib/
