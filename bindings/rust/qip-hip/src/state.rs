@@ -28,6 +28,25 @@ pub(crate) fn check(rc: i32) -> Result<(), HipError> {
     Err(HipError { code: rc, message })
 }
 
+/// The term arrays of `include/qip_hipx.h` for the diagonal calls: (term_start, qubits, paulis, coefficients), every array with one
+/// spare element so that none is a dangling pointer for an empty list.
+fn diagonal_arrays(terms: &[Vec<(u64, u8)>], coeffs: &[f64]) -> (Vec<u64>, Vec<u64>, Vec<u8>, Vec<f64>) {
+    let mut start = vec![0u64];
+    let (mut qubits, mut paulis) = (Vec::new(), Vec::new());
+    for term in terms {
+        for &(q, p) in term {
+            qubits.push(q);
+            paulis.push(p);
+        }
+        start.push(qubits.len() as u64);
+    }
+    qubits.push(0);
+    paulis.push(0);
+    let mut c = coeffs.to_vec();
+    c.push(0.0);
+    (start, qubits, paulis, c)
+}
+
 pub struct HipState<P: HipPrecision = f64> {
     n: usize,
     h: *mut sys::qip_hip_state,
@@ -172,6 +191,27 @@ impl<P: HipPrecision> HipState<P> {
         check(unsafe {
             sys_ext::qipx_state_apply_pauli_rotations(self.h, start.as_ptr(), qubits.as_ptr(), paulis.as_ptr(), angles.as_ptr(), terms.len() as u64)
         })
+    }
+    /// psi[j] <- exp(-i gamma D(j)) psi[j] for the diagonal sum D = sum_t coeffs[t] P_t (`include/qip_hipx.h`): terms as for
+    /// `expect_pauli` with factors I (0) and Z (3) only.  ONE in-place pass whatever the number of terms; queued on the stream,
+    /// returns without waiting.
+    pub fn apply_diagonal(&mut self, terms: &[Vec<(u64, u8)>], coeffs: &[f64], gamma: f64) -> Result<(), HipError> {
+        assert_eq!(terms.len(), coeffs.len(), "one coefficient per term");
+        let (start, qubits, paulis, c) = diagonal_arrays(terms, coeffs);
+        check(unsafe {
+            sys_ext::qipx_state_apply_diagonal(self.h, start.as_ptr(), qubits.as_ptr(), paulis.as_ptr(), c.as_ptr(), terms.len() as u64, gamma)
+        })
+    }
+    /// (sum_j |psi_j|^2 D(j), sum_j |psi_j|^2 D(j)^2) for the same D: raw, in double for both precisions, one pass; the state is
+    /// not changed.
+    pub fn expect_diagonal(&self, terms: &[Vec<(u64, u8)>], coeffs: &[f64]) -> Result<(f64, f64), HipError> {
+        assert_eq!(terms.len(), coeffs.len(), "one coefficient per term");
+        let (start, qubits, paulis, c) = diagonal_arrays(terms, coeffs);
+        let mut out = [0f64; 2];
+        check(unsafe {
+            sys_ext::qipx_state_expect_diagonal(self.h, start.as_ptr(), qubits.as_ptr(), paulis.as_ptr(), c.as_ptr(), terms.len() as u64, out.as_mut_ptr())
+        })?;
+        Ok((out[0], out[1]))
     }
     /// self <- H src, or self + H src when `accumulate`, for H = sum_t coeffs[t] P_t (`include/qip_hipx.h`): terms as for
     /// `expect_pauli`, coefficients as `(re, im)`; `src` is another state of the same size, precision and device and is not

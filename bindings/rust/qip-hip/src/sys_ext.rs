@@ -107,4 +107,26 @@ extern "C" {
     /// values[2i] + i values[2i+1] = <bras[i]|ket>, 1 <= count <= 16, in double for both precisions, one pass over all of them; a
     /// batch equals its single-bra calls bit for bit.  No state is changed.
     pub fn qipx_state_inner_products(bras: *const *mut qip_hip_state, count: u32, ket: *mut qip_hip_state, values: *mut c_double) -> c_int;
+    /// psi[j] <- exp(-i gamma D(j)) psi[j], D(j) = sum_t coeffs[t] (-1)^popcount(j & z_t): the terms as for `qipx_state_expect_pauli`,
+    /// factors I and Z only.  ONE in-place pass whatever `count` is; queued on the handle's stream, returns without waiting.
+    pub fn qipx_state_apply_diagonal(
+        s: *mut qip_hip_state,
+        term_start: *const u64,
+        qubits: *const u64,
+        paulis: *const u8,
+        coeffs: *const c_double,
+        count: u64,
+        gamma: c_double,
+    ) -> c_int;
+    /// moments[0] = sum_j |psi_j|^2 D(j), moments[1] = sum_j |psi_j|^2 D(j)^2 for the same D: raw, in double for both precisions,
+    /// one pass; the state is not changed.  Complete when it returns.
+    pub fn qipx_state_expect_diagonal(
+        s: *mut qip_hip_state,
+        term_start: *const u64,
+        qubits: *const u64,
+        paulis: *const u8,
+        coeffs: *const c_double,
+        count: u64,
+        moments: *mut c_double,
+    ) -> c_int;
 }

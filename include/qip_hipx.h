@@ -310,6 +310,71 @@ int qipx_state_linear_combination(qip_hip_state* dst, qip_hip_state* const* srcs
  * on all of them and complete when it returns.  With count > 0 a null `bras` or `values` is QIP_ERR_INVALID. */
 int qipx_state_inner_products(qip_hip_state* const* bras, uint32_t count, qip_hip_state* ket, double* values);
 
+/* Diagonal Pauli sums of any size in one pass: the cost layer exp(-i gamma D) of QAOA and the first two moments of a cost
+ * Hamiltonian D = sum_t coeffs[t] * Z-string_t (MaxCut / SK / Ising energies, penalty terms, any objective on bit strings expanded
+ * in Z monomials).  (Purely additive again.)
+ *
+ * The terms are given exactly as for qipx_state_expect_pauli above (the same arrays, the same codes, qubit q = index bit n-1-q)
+ * and are checked by the same code with the same messages; every factor must be I or Z, coeffs[t] is real.  With z_t the z mask
+ * of term t,
+ *   D(j) = sum_t coeffs[t] * (-1)^popcount(j & z_t).
+ *   apply:   psi[j] <- exp(-i * gamma * D(j)) * psi[j]
+ *   expect:  moments[0] = sum_j |psi_j|^2 D(j),   moments[1] = sum_j |psi_j|^2 D(j)^2     (raw: not divided by the norm)
+ * An empty term (and a term of I factors only) is the constant coeffs[t]: a global phase, an offset.  Repeated z masks are allowed
+ * and add.
+ *
+ * Cost.  ONE kernel launch whatever `count` is; every amplitude is read once (and, by apply, written once, in place).  The
+ * vector is cut into tiles of 2^L contiguous amplitudes, L = min(n, 12), j = (h << L) | l.  With z_t = (zhi_t << L) | zlo_t the 2^L
+ * energies of tile h are the Walsh-Hadamard transform of a_h[m] = sum_{t : zlo_t = m} k_t (-1)^popcount(h & zhi_t): a tile costs
+ * `count` sign evaluations, spread over the block's lanes by low mask, and L additions per amplitude, instead of `count` per
+ * amplitude.  (The terms of ONE low mask are summed by one lane: a call whose terms all share a low mask, all of them above bit
+ * 12 for instance, serialises there.)  The term table lives in a device buffer of the handle, grown on demand and freed with it.
+ * tools/bench_diagonal.py and profiles/diagonal.md hold the measured times against the rotation and expect_pauli paths.
+ *
+ * Arithmetic.  k_t = fl(gamma * coeffs[t]) in double on the host (apply), k_t = coeffs[t] (expect).  The energy E^(j) is formed IN
+ * DOUBLE for both precisions: a_h[m] is the sum of (+-)k_t over the terms of low mask m in the order of the call, starting from
+ * +0 (the sign an exact flip); then L butterfly stages (u, v) -> (u + v, u - v) over index bit 0, 1, .., L - 1 in that order, v
+ * the entry whose stage bit is set.  E^(j) is a function of the call and of j only, not of the grid or of the element packing
+ * (option "packed_f32"): same call, same bits.  No atomics anywhere.
+ *   apply    (c, s) = (cos E^, sin E^) evaluated in double and rounded once to the state's precision; the new components are
+ *            fl(fl(c re) + fl(s im)) and fl(fl(c im) - fl(s re)), never fused, no special case for zeros, as in the rotation kernel.
+ *   expect   p = fl(fl(re re) + fl(im im)) in double (f32 amplitudes widened first, as in qipx_state_expect_pauli); the lane adds
+ *            fl(p E^) and fl(fl(p E^) E^) to its two running sums; then wave, block, and two partial sums per block in the
+ *            handle's reduction scratch, which the host adds in block order.  The longest chain of additions is
+ *              c(n) = 16 * max(1, 2^(n-24)) + 6 + 4 + min(4096, 2^(n-12))      (n >= 12; max(1, 2^(n-8)) + 11 below)
+ *            (a lane's 16 amplitudes of each of its block's tiles, the wave's tree, the block's waves, the host's blocks):
+ *            5130 at n = 30.
+ *
+ * Error statement.  With A = sum_t |k_t| and u the unit roundoff of the state (2^-53, 2^-24), to first order
+ *   |E^(j) - gamma D(j)| <= (count + L + 1) 2^-53 A          (one rounding of k_t, at most count + L additions)
+ *   apply:   |psi'[j] - exp(-i gamma D(j)) psi[j]| <= [12 u + (count + L + 8) 2^-53 A] |psi[j]|
+ *   expect:  |moments[0] - exact| <= (count + L + c(n) + 6) 2^-53 A |psi|^2,
+ *            |moments[1] - exact| <= (2 (count + L) + c(n) + 10) 2^-53 A^2 |psi|^2.
+ * 12 u is the bar of one unit-modulus complex multiply with rounded c and s (the rotation call's, a double-precision reference
+ * included); the 8, 6 and 10 hold the few ulps of the double sine and cosine, the roundings of p and of the products, and margin.
+ * These are the constants tests/diagonal_ref.py derives and the GPU tests hold both calls to.
+ * Large angles are carried by the A term alone: the sine and cosine are double-precision evaluations of a double-precision
+ * angle for Complex<f32> states too.
+ *
+ * Calling contract.  apply: the state is changed in place; the launch is queued on the handle's stream and the call returns
+ * without waiting, like qipx_state_apply_pauli_rotations (a relabelled state, option "tile_relabel" = 3, is put back in the
+ * caller's order first).  The caller's arrays are not read after the call returns: the table travels through a pinned buffer of
+ * the handle; there are two, taken in turn, and a call waits only for the upload of the call before the previous one — never for a
+ * kernel — before it rewrites its buffer.
+ * expect: the state is not changed (relabelled: settled first, as by the measurement calls); the call is ordered after the work
+ * queued on the handle and COMPLETE WHEN IT RETURNS.  count == 0: apply does nothing, expect returns (0, 0) (null arrays allowed).
+ * Each of these is refused with a message before anything is queued, the state untouched: a null handle (QIP_ERR_INVALID: there
+ * is no host fall-back); an unusable handle (QIP_ERR_DEVICE); with count > 0 a null array or a null `moments`, a non-finite
+ * coefficient, a non-finite gamma or a non-finite product of the two (the message names the term), a term with an X or Y factor
+ * ("term %llu is not diagonal") or any term error of qipx_state_expect_pauli (all QIP_ERR_INVALID); more than 2^20 terms
+ * (QIP_ERR_UNSUPPORTED: the cap of one call).
+ *
+ * There is no option, and the launches are not a kernel class of the profile. */
+int qipx_state_apply_diagonal(qip_hip_state* s, const uint64_t* term_start, const uint64_t* qubits, const uint8_t* paulis,
+                              const double* coeffs, uint64_t count, double gamma);
+int qipx_state_expect_diagonal(qip_hip_state* s, const uint64_t* term_start, const uint64_t* qubits, const uint8_t* paulis,
+                               const double* coeffs, uint64_t count, double* moments /* [2] */);
+
 #ifdef __cplusplus
 }
 #endif

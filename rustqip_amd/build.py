@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 # only exports are the C ABI (csrc/exports.map)
 UNITS = ["qip_core", "qip_launch", "qip_tile_sched", "qip_circuit", "qip_tile_interp", "qip_jit", "qip_slice", "qip_host", "qip_measure", "qip_pauli", "qip_dist"]
 HEADERS = [os.path.join(CSRC, h) for h in ("qip_kernels.h", "qip_internal.h", "qip_jit.h", "qip_tile.h", "qip_tile_wire.h", "qip_pauli_plan.h",
-                                               "qip_pauli_kernels.h")] + [
+                                               "qip_pauli_kernels.h", "qip_diag_plan.h", "qip_diag_kernels.h")] + [
     os.path.join(HERE, "..", "include", "qip_hip.h"), os.path.join(HERE, "..", "include", "qip_hip_debug.h"),
     os.path.join(HERE, "..", "include", "qip_hipx.h")]
 OBJDIR = os.path.join(HERE, "build")

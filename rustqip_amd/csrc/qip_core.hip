@@ -464,6 +464,11 @@ extern "C" int qip_hip_state_destroy(qip_hip_state* s) try {
   if (s->d_partial) (void)hipFree(s->d_partial);
   if (s->d_ticket) (void)hipFree(s->d_ticket);
   if (s->d_sample) (void)hipFree(s->d_sample);
+  if (s->d_diag) (void)hipFree(s->d_diag);
+  for (int i = 0; i < 2; ++i) {
+    if (s->h_diag[i]) (void)hipHostFree(s->h_diag[i]);
+    if (s->diag_uploaded[i]) (void)hipEventDestroy(s->diag_uploaded[i]);
+  }
   if (s->owns_stream && s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
   return QIP_OK;

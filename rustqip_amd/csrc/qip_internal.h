@@ -9,7 +9,8 @@
 //   qip_host.hip      host-pointer twins of the reference functions
 //   qip_measure.hip   measurement, sampling, reduced density matrices
 //   qip_pauli.hip     Pauli-string calls (expectation values, rotations, sums, matrix elements) and vector arithmetic of resident
-//                     states, over qip_pauli_plan.h (terms, planners, pass geometry: plain C++) and qip_pauli_kernels.h
+//                     states, over qip_pauli_plan.h (terms, planners, pass geometry: plain C++) and qip_pauli_kernels.h; the
+//                     diagonal Pauli sums in one pass, over qip_diag_plan.h (plain C++) and qip_diag_kernels.h
 //   qip_dist.hip      the sharded state (planner, pack sweep, exchange)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -180,6 +181,14 @@ struct qip_hip_state {
   int64_t expect_group = kExpectGroupDefault;  // option "expect_group": most terms of qipx_state_expect_pauli that share a pass
   int64_t rotate_group = kRotateGroupDefault;  // option "rotate_group": most terms of qipx_state_apply_pauli_rotations that share a pass
   int64_t sum_group = kSumGroupDefault;  // option "sum_group": most terms of qipx_state_apply_pauli_sum that share a pass
+  // qipx_state_apply_diagonal / expect_diagonal (qip_pauli.hip): the term table on the device and TWO pinned host copies used in
+  // turn to feed its stream-ordered upload, each with the event recorded behind its last upload (a host copy is rewritten only
+  // once that event has passed: a call waits for the upload of the call before the previous one, never for the previous call)
+  void* d_diag = nullptr;
+  void* h_diag[2] = {nullptr, nullptr};
+  size_t diag_cap = 0;
+  hipEvent_t diag_uploaded[2] = {nullptr, nullptr};
+  uint32_t diag_turn = 0;  // the host copy the next call takes
   // options
   int64_t force_generic = 0;
   int64_t profile = 0;

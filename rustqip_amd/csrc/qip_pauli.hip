@@ -6,9 +6,11 @@
 //           family's own tail; the kernel instantiation (packed / pair / slot capacity) is chosen by pauli_dispatch
 // The geometry depends on n, the precision and the class of the x mask only, never on the group: together with the kernels'
 // per-slot arithmetic that makes a result a function of the states and its term.
+// The diagonal sums (apply_diagonal, expect_diagonal) take all their terms in ONE pass of their own: see their section.
 #include "qip_internal.h"
 #include "../../include/qip_hipx.h"
 #include "qip_pauli_kernels.h"
+#include "qip_diag_kernels.h"
 
 // ---- shared by every call -----------------------------------------------------------------------------------------------------
 // `what`: the call's name in a refusal
@@ -223,6 +225,135 @@ extern "C" int qipx_state_apply_pauli_rotations(qip_hip_state* s, const uint64_t
     if (!std::isfinite(angles[t])) return fail(QIP_ERR_INVALID, "pauli_rotations: the angle of term %llu is not finite", (unsigned long long)t);
   if (!s->layout.empty()) QCHK(state_settle(s));  // (a relabelled state: the caller's order first, as by STATE_ENTER)
   return s->dtype == QIP_C64 ? rotate_t<double>(s, terms, angles) : rotate_t<float>(s, terms, angles);
+} QIP_CATCH_ALL
+
+// ---- diagonal Pauli sums D = sum_t c_t Z-string_t in one pass: exp(-i gamma D) in place, <D> and <D^2> ---------------------------------
+//   check   the terms as every call above (pauli_terms), then: no X or Y factor, finite coefficients, k_t = fl(gamma c_t) finite
+//   plan    qip_diag_plan.h: every z mask split at the tile boundary, the terms sorted stably by low mask into groups
+//   table   terms, group starts and group masks in ONE handle-owned device buffer, uploaded through one of two handle-owned pinned
+//           copies, taken in turn
+//   launch  ONE k_diag_phase / k_diag_moments launch whatever the number of terms (qip_diag_kernels.h)
+// The upload is stream-ordered and the phase call returns without waiting, so two things must hold.  The device table is rewritten
+// only by a copy queued on the stream behind the kernel that read it.  A pinned copy is rewritten by the host only after the
+// event recorded behind ITS last upload has passed (diag_upload waits for it: with two copies taken in turn that is the upload of
+// the call before the previous one, so one call's work can still be queued while the next one is prepared).
+// Growing the buffers waits for the stream first.
+static int diag_check(const char* what, qip_hip_state* s, const uint64_t* term_start, const uint64_t* qubits, const uint8_t* paulis,
+                      const double* coeffs, uint64_t count, double gamma, DiagPlan* plan) {
+  if (count > kDiagMaxTerms)
+    return fail(QIP_ERR_UNSUPPORTED, "%s: %llu terms, at most %llu are supported", what, (unsigned long long)count, (unsigned long long)kDiagMaxTerms);
+  if (!coeffs) return fail(QIP_ERR_INVALID, "%s: null coefficient array", what);
+  std::vector<PauliTerm> terms;
+  QCHK(pauli_terms(what, s->n, term_start, qubits, paulis, count, &terms));
+  for (uint64_t t = 0; t < count; ++t)
+    if (terms[t].x != 0) return fail(QIP_ERR_INVALID, "%s: term %llu is not diagonal", what, (unsigned long long)t);
+  if (!std::isfinite(gamma)) return fail(QIP_ERR_INVALID, "%s: gamma is not finite", what);
+  std::vector<uint64_t> z(count);
+  std::vector<double> k(count);
+  for (uint64_t t = 0; t < count; ++t) {
+    if (!std::isfinite(coeffs[t])) return fail(QIP_ERR_INVALID, "%s: the coefficient of term %llu is not finite", what, (unsigned long long)t);
+    z[t] = terms[t].z;
+    k[t] = gamma * coeffs[t];
+    if (!std::isfinite(k[t])) return fail(QIP_ERR_INVALID, "%s: gamma times the coefficient of term %llu is not finite", what, (unsigned long long)t);
+  }
+  *plan = diag_plan(s->n, z.data(), k.data(), (size_t)count);
+  return QIP_OK;
+}
+
+static int diag_upload(qip_hip_state* s, const DiagPlan& plan, const DiagGeom& g, DiagSumDesc* d) {
+  const size_t nterms = plan.terms.size(), ngroups = plan.group_mask.size();
+  const size_t off_start = nterms * sizeof(DiagTerm), off_mask = off_start + (ngroups + 1) * sizeof(uint32_t);
+  const size_t bytes = off_mask + ngroups * sizeof(uint32_t);
+  if (bytes > s->diag_cap) {
+    HIPCHK(hipStreamSynchronize(s->stream));  // (a kernel may still read the old table, a copy the old host buffers)
+    if (s->d_diag) HIPCHK(hipFree(s->d_diag));
+    s->d_diag = nullptr;
+    for (int i = 0; i < 2; ++i) {
+      if (s->h_diag[i]) HIPCHK(hipHostFree(s->h_diag[i]));
+      s->h_diag[i] = nullptr;
+    }
+    s->diag_cap = 0;
+    const size_t cap = std::max<size_t>(bytes + bytes / 2, 1 << 16);
+    HIPCHK(hipMalloc(&s->d_diag, cap));
+    for (int i = 0; i < 2; ++i) HIPCHK(hipHostMalloc(&s->h_diag[i], cap, hipHostMallocDefault));
+    s->diag_cap = cap;
+  }
+  const uint32_t turn = s->diag_turn;
+  s->diag_turn ^= 1u;
+  if (s->diag_uploaded[turn]) HIPCHK(hipEventSynchronize(s->diag_uploaded[turn]));  // this copy's last upload has left it
+  else HIPCHK(hipEventCreateWithFlags(&s->diag_uploaded[turn], hipEventDisableTiming));
+  char* h = (char*)s->h_diag[turn];
+  memcpy(h, plan.terms.data(), nterms * sizeof(DiagTerm));
+  memcpy(h + off_start, plan.group_start.data(), (ngroups + 1) * sizeof(uint32_t));
+  memcpy(h + off_mask, plan.group_mask.data(), ngroups * sizeof(uint32_t));
+  HIPCHK(hipMemcpyAsync(s->d_diag, h, bytes, hipMemcpyHostToDevice, s->stream));
+  HIPCHK(hipEventRecord(s->diag_uploaded[turn], s->stream));
+  d->terms = (const DiagTerm*)s->d_diag;
+  d->group_start = (const uint32_t*)((const char*)s->d_diag + off_start);
+  d->group_mask = (const uint32_t*)((const char*)s->d_diag + off_mask);
+  d->ngroups = (uint32_t)ngroups;
+  d->tile_bits = g.tile_bits;
+  d->ntiles = g.ntiles;
+  d->tiles_per_block = g.tiles_per_block;
+  return QIP_OK;
+}
+
+static DiagGeom diag_geom_of(const qip_hip_state* s) {
+#ifdef QIP_HIP_TUNING
+  return diag_geom(s->n, s->dtype == QIP_C32 && s->packed_f32);
+#else
+  return diag_geom(s->n, s->dtype == QIP_C32);  // (Complex<f32> is always read in 16-byte elements of two amplitudes)
+#endif
+}
+
+extern "C" int qipx_state_apply_diagonal(qip_hip_state* s, const uint64_t* term_start, const uint64_t* qubits, const uint8_t* paulis,
+                                         const double* coeffs, uint64_t count, double gamma) try {
+  STATE_ENTER_RAW(s);
+  if (count == 0) return QIP_OK;
+  DiagPlan plan;
+  QCHK(diag_check("apply_diagonal", s, term_start, qubits, paulis, coeffs, count, gamma, &plan));
+  if (!s->layout.empty()) QCHK(state_settle(s));  // (a relabelled state: the caller's order first, as by STATE_ENTER)
+  const DiagGeom g = diag_geom_of(s);
+  DiagSumDesc d;
+  QCHK(diag_upload(s, plan, g, &d));
+  const dim3 grid(g.nblocks), block(kBlock);
+  if (s->dtype == QIP_C64) hipLaunchKernelGGL((k_diag_phase<double>), grid, block, 0, s->stream, (amp_t<double>*)s->cur, d);
+  else if (g.shift) hipLaunchKernelGGL((k_diag_phase<float, f32x4>), grid, block, 0, s->stream, (f32x4*)s->cur, d);
+#ifdef QIP_HIP_TUNING  // (option "packed_f32" = 0 exists in a tuning build only: the product build has no plain Complex<f32> walk)
+  else hipLaunchKernelGGL((k_diag_phase<float>), grid, block, 0, s->stream, (amp_t<float>*)s->cur, d);
+#endif
+  HIPCHK(hipGetLastError());
+  return QIP_OK;
+} QIP_CATCH_ALL
+
+extern "C" int qipx_state_expect_diagonal(qip_hip_state* s, const uint64_t* term_start, const uint64_t* qubits, const uint8_t* paulis,
+                                          const double* coeffs, uint64_t count, double* moments) try {
+  STATE_ENTER(s);
+  if (count == 0) {
+    if (moments) moments[0] = moments[1] = 0.0;
+    return QIP_OK;
+  }
+  if (!moments) return fail(QIP_ERR_INVALID, "expect_diagonal: null result array");
+  DiagPlan plan;
+  QCHK(diag_check("expect_diagonal", s, term_start, qubits, paulis, coeffs, count, 1.0, &plan));  // (k_t = c_t: 1.0 * c is exact)
+  const DiagGeom g = diag_geom_of(s);
+  QCHK(ensure_partial(s, 2 * (size_t)g.nblocks));
+  DiagSumDesc d;
+  QCHK(diag_upload(s, plan, g, &d));
+  const dim3 grid(g.nblocks), block(kBlock);
+  if (s->dtype == QIP_C64) hipLaunchKernelGGL((k_diag_moments<double>), grid, block, 0, s->stream, (const amp_t<double>*)s->cur, d, s->d_partial);
+  else if (g.shift) hipLaunchKernelGGL((k_diag_moments<float, f32x4>), grid, block, 0, s->stream, (const f32x4*)s->cur, d, s->d_partial);
+#ifdef QIP_HIP_TUNING
+  else hipLaunchKernelGGL((k_diag_moments<float>), grid, block, 0, s->stream, (const amp_t<float>*)s->cur, d, s->d_partial);
+#endif
+  HIPCHK(hipGetLastError());
+  std::vector<double> part(2 * (size_t)g.nblocks);
+  HIPCHK(hipMemcpyAsync(part.data(), s->d_partial, part.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  double m1 = 0, m2 = 0;
+  for (uint32_t b = 0; b < g.nblocks; ++b) m1 += part[b], m2 += part[g.nblocks + b];
+  moments[0] = m1, moments[1] = m2;
+  return QIP_OK;
 } QIP_CATCH_ALL
 
 // ---- two states and Pauli strings: dst (+)= (sum_t c_t P_t) src and <bra| P_t |ket> ---------------------------------------------

@@ -409,6 +409,21 @@ template <typename P> class HipState {
     paulis.push_back(0);
     check(qipx_state_apply_pauli_rotations(h_, start.data(), qubits.data(), paulis.data(), angles.data(), terms.size()));
   }
+  /// psi[j] <- exp(-i gamma D(j)) psi[j] for the diagonal sum D = sum_t coeffs[t] P_t (qip_hipx.h): terms as for expect_pauli
+  /// with factors I (0) and Z (3) only.  ONE in-place pass whatever the number of terms; queued on the stream, returns without
+  /// waiting.
+  void apply_diagonal(const std::vector<std::vector<std::pair<size_t, int>>>& terms, const std::vector<double>& coeffs, double gamma = 1.0) {
+    const DiagonalArrays a("apply_diagonal", terms, coeffs);
+    check(qipx_state_apply_diagonal(h_, a.start.data(), a.qubits.data(), a.paulis.data(), a.coeffs.data(), terms.size(), gamma));
+  }
+  /// (sum_j |psi_j|^2 D(j), sum_j |psi_j|^2 D(j)^2) for the same D (qip_hipx.h): raw, in double for both precisions, one pass; the
+  /// state is not changed.
+  std::pair<double, double> expect_diagonal(const std::vector<std::vector<std::pair<size_t, int>>>& terms, const std::vector<double>& coeffs) const {
+    const DiagonalArrays a("expect_diagonal", terms, coeffs);
+    double m[2] = {0.0, 0.0};
+    check(qipx_state_expect_diagonal(h_, a.start.data(), a.qubits.data(), a.paulis.data(), a.coeffs.data(), terms.size(), m));
+    return {m[0], m[1]};
+  }
   /// *this <- H src, or *this + H src when `accumulate`, for H = sum_t coeffs[t] P_t (qip_hipx.h): terms as for expect_pauli,
   /// `src` another state of the same n, precision and device (not changed).  Complete when it returns.
   void apply_pauli_sum(HipState& src, const std::vector<std::vector<std::pair<size_t, int>>>& terms,
@@ -506,6 +521,27 @@ template <typename P> class HipState {
   qip_hip_state* handle() { return h_; }
 
  private:
+  /// the term arrays of qip_hipx.h for the diagonal calls; every array has one spare element (never a null data())
+  struct DiagonalArrays {
+    std::vector<uint64_t> start, qubits;
+    std::vector<uint8_t> paulis;
+    std::vector<double> coeffs;
+    DiagonalArrays(const char* what, const std::vector<std::vector<std::pair<size_t, int>>>& terms, const std::vector<double>& c)
+        : start(1, 0), coeffs(c) {
+      if (c.size() != terms.size()) throw std::invalid_argument(std::string(what) + ": one coefficient per term");
+      for (const auto& term : terms) {
+        for (const auto& f : term) {
+          if (f.second < 0 || f.second > 255) throw std::invalid_argument(std::string(what) + ": Pauli code out of range");
+          qubits.push_back(f.first);
+          paulis.push_back(uint8_t(f.second));
+        }
+        start.push_back(qubits.size());
+      }
+      qubits.push_back(0);
+      paulis.push_back(0);
+      coeffs.push_back(0.0);
+    }
+  };
   size_t n_;
   qip_hip_state* h_ = nullptr;
 };

@@ -529,6 +529,48 @@ class HipState:
         for _ in range(int(steps)):
             self.apply_pauli_rotations(terms, c * float(dt))
 
+    def _diagonal_args(self, terms, coeffs):
+        terms = list(terms)
+        c = np.ascontiguousarray(np.asarray(coeffs, dtype=np.float64).reshape(-1))
+        if len(c) != len(terms):
+            raise CircuitError(f"{len(terms)} terms but {len(c)} coefficients")
+        start, qubits, paulis, count = _pauli_terms(self.n, terms)
+        return start, qubits, paulis, c, count
+
+    def apply_diagonal(self, terms, coeffs, gamma: float = 1.0) -> None:
+        """psi[j] <- exp(-i gamma D(j)) psi[j] for the diagonal sum D = sum_t coeffs[t] * terms[t] (include/qip_hipx.h): the term
+        forms of expect_pauli with factors I and Z only, real coefficients.  ONE in-place pass over the vector whatever the number
+        of terms (a QAOA cost layer, an Ising / MaxCut phase separator); the energy is formed in double for both precisions.
+        Queued on the handle's stream: returns without waiting.  Against apply_pauli_rotations on the same terms, measured at n = 30
+        (profiles/diagonal.md): one rotation pass of up to four terms is 1.0 ms cheaper (5.6 against 6.6 ms), at 16 terms this
+        call is ahead (6.7 against 7.0 ms), at 30 terms 6.6 against 13.4 ms, at 435 terms 6.9 against 195 ms."""
+        start, qubits, paulis, c, count = self._diagonal_args(terms, coeffs)
+        _check(_ffi.lib.qipx_state_apply_diagonal(self._h, start, qubits, paulis, c.ctypes.data_as(C.POINTER(C.c_double)), count,
+                                                  float(gamma)))
+
+    def expect_diagonal(self, terms, coeffs) -> Tuple[float, float]:
+        """(sum_j |psi_j|^2 D(j), sum_j |psi_j|^2 D(j)^2) for the diagonal sum D = sum_t coeffs[t] * terms[t]: the raw first and
+        second moment of a cost Hamiltonian (not divided by the norm) from ONE pass over the vector whatever the number of
+        terms, in double for both precisions.  The state is not changed."""
+        start, qubits, paulis, c, count = self._diagonal_args(terms, coeffs)
+        out = (C.c_double * 2)()
+        _check(_ffi.lib.qipx_state_expect_diagonal(self._h, start, qubits, paulis, c.ctypes.data_as(C.POINTER(C.c_double)), count, out))
+        return float(out[0]), float(out[1])
+
+    def qaoa_layers(self, terms, coeffs, gammas, betas) -> None:
+        """The QAOA ansatz on the cost D = sum_t coeffs[t] * terms[t]: per layer apply_diagonal(terms, coeffs, gamma), then the
+        mixer exp(-i beta X) = RX(2 beta) on every qubit through apply_ops.  Everything is queued on the handle's stream."""
+        from .ops import make_matrix_op
+
+        terms = list(terms)
+        gammas, betas = [float(g) for g in gammas], [float(b) for b in betas]
+        if len(gammas) != len(betas):
+            raise CircuitError(f"{len(gammas)} gammas but {len(betas)} betas")
+        for gamma, beta in zip(gammas, betas):
+            self.apply_diagonal(terms, coeffs, gamma)
+            c, s = np.cos(beta), np.sin(beta)
+            self.apply_ops([make_matrix_op([qb], [c, -1j * s, -1j * s, c]) for qb in range(self.n)])
+
     def _partner(self, other: "HipState", what: str) -> None:
         if not isinstance(other, HipState):
             raise CircuitError(f"{what}: the other state is not a HipState")
