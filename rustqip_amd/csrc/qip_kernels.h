@@ -849,8 +849,10 @@ __global__ __launch_bounds__(kBlock) void k_gate_kq(amp_t<T>* __restrict__ st, u
 //     stores them back in place with 16-B accesses;
 //   * the A operand (gate matrix in that row/column order) is precomputed on the host per lane
 //     (afrag[(rb*KS + s)*64 + lane]) and held in registers across the wave's grid-stride loop.
-// Rounding: an MFMA is a k-ordered fma chain, so results differ from the reference's unfused fold
-// by a few ulp (covered by the 1e-12 bar); 0/1 permutation matrices stay exact for finite data.
+// Rounding: an MFMA is a k-ordered fma chain, so results differ from the reference's unfused fold: measured
+// against a long-double reference (profiles/dense_accuracy.md, e as defined at mfma3_item below) rms(e) is
+// 0.8 - 1.34 x the fold's and max|e| <= 11.6 against the derived bound 4 * 2^k + 8 = 40 / 72 / 136; integer
+// inputs and 0/1 permutation matrices stay exact for finite data.
 struct MfmaDesc {
   uint32_t tau[8];  // target bit positions, ascending
 };
@@ -878,7 +880,12 @@ template <> struct Acc4<float> { using type = v4f32; };
 // keeps a 0/1 matrix exact (every sum is one amplitude plus zeros), which the three-product form would not ((a + b) - b).
 // Fragments: frag[((rb * NP + part) * (S/4) + s) * 64 + lane], NP = 3 (parts P, R, Q) or 1; 16 COMPLEX rows per block rb.
 // C/D layout as above: a lane ends up with re (chain `re`) and im (chain `im`) of the amplitudes c~' = 16 rb + 4 reg + q, i.e.
-// its own amplitudes m' = 4 rb + reg.  Rounding: a few ulp from the unfused fold (1e-12 bar), like every matrix-core form.
+// its own amplitudes m' = 4 rb + reg.  Rounding, measured against a long-double reference (profiles/dense_accuracy.md; e = error
+// per real component in units of u * a_r, a_r = sum_c (|Re g_rc| + |Im g_rc|)(|Re x_c| + |Im x_c|), which bounds the cancelled
+// G_re X_re too): three products rms(e) 0.17 - 0.24 on normalised states, 1.3 - 1.4 x the unfused fold's (up to 1.7 x on nearly
+// cancelling groups, 1.0 x for Complex<f64> at k = 10, whose item is two phases), max|e| <= 17.4 over every input class against
+// the derived bound 4 * 2^k + 8 = 264 ... 4104; two products 0.92 - 1.01 x the fold's.  tests/test_gpu_a_dense_accuracy.py holds
+// every form to that bound, to 4 x the fold's rms and 8 x its maximum, on unnormalised and wide-range states as on normalised ones.
 template <typename T, int K, int NP>
 __device__ __forceinline__ void mfma3_item(const T (&a)[(1 << K) / 16][NP][(1 << K) / 4], const amp_t<T> (&x)[(1 << K) / 4],
                                            amp_t<T> (&y)[(1 << K) / 4]) {

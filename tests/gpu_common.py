@@ -5,7 +5,15 @@ Everything goes through the C ABI (ctypes -> libqip_hip.so -> HIP kernels).  Bar
   * everything else: |delta| <= 1e-12 per amplitude (f64), 1e-5 (f32) — and, because kernels and
     oracle are both built without FMA contraction and fold in the same order, the 1-qubit,
     phase, diagonal and literal-gather kernels are additionally expected to be bit-equal,
-    which is asserted where it has been observed.
+    which is asserted where it has been observed;
+  * the matrix-core dense kernels (k_gate_kq_mfma, k_gate_tile_mfma, k_gate_big_mfma, k_gate_huge_mfma), which fold fused, in
+    another order and from k = 5 with three real products, are additionally held to a scale-free bar
+    (tests/test_gpu_a_dense_accuracy.py, tests/numeric_ref.py): per real component e = (got - exact) / (u a_r), exact from a
+    reference in higher precision (long double for f64, f64 for f32), a_r = sum_c (|Re g_rc| + |Im g_rc|) (|Re x_c| + |Im x_c|),
+    u = 2^-53 / 2^-24; max|e| <= 4 * 2^k + 8 (derived), rms(e) <= 4 x and max|e| <= 8 x the oracle's on the same samples —
+    on unnormalised, wide-range, nearly real and nearly cancelling states and on non-unitary matrices as tightly as on a
+    normalised state; K(2^s x) == 2^s K(x) and K_{2^s G}(x) == 2^s K_G(x) bit for bit; integer inputs exact.  The absolute
+    bars above stay as they are: on a normalised Complex<f32> state of 19 qubits 1e-5 is a relative bar of one per cent.
 """
 import cmath
 import math
