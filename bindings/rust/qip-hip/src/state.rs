@@ -269,6 +269,15 @@ impl<P: HipPrecision> HipState<P> {
         check(unsafe { sys_ext::qipx_state_reduced_density(self.h, indices.as_ptr(), indices.len() as u32, flat.as_mut_ptr()) })?;
         Ok(flat.chunks(2 * m).map(|row| row.chunks(2).map(|c| (c[0], c[1])).collect()).collect())
     }
+    /// The raw reduced transition matrix of up to three qubits (`include/qip_hipx.h`), `self` the bra: `2^k` rows of `2^k` entries
+    /// `(re, im)`, `m[a][a'] = sum_b ket[a,b] conj(self[a',b])`, bit `i` of `a` = qubit `indices[i]`; `<self| A |ket> = Tr(A m)` for
+    /// every operator `A` on those qubits.  Neither state is changed.
+    pub fn transition_matrix(&mut self, ket: &mut HipState<P>, indices: &[u64]) -> Result<Vec<Vec<(f64, f64)>>, HipError> {
+        let m = 1usize << indices.len().min(3);
+        let mut flat = vec![0f64; 2 * m * m];
+        check(unsafe { sys_ext::qipx_state_transition_matrix(self.h, ket.h, indices.as_ptr(), indices.len() as u32, flat.as_mut_ptr()) })?;
+        Ok(flat.chunks(2 * m).map(|row| row.chunks(2).map(|c| (c[0], c[1])).collect()).collect())
+    }
     /// `self[j] <- own * self[j] + sum_i coeffs[i] * others[i][j]` in one pass (`include/qip_hipx.h`), coefficients as
     /// `(re, im)`: `self` is the first source when `own` is given (two `&mut` to one state cannot be had, so the state itself
     /// is named this way), at most 16 sources in all, none: `self <- 0`.  With `want_norm` the pass also returns

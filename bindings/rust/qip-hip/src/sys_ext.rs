@@ -94,6 +94,10 @@ extern "C" {
     /// rho[2 (a M + a')] + i rho[.. + 1] = sum_b psi[a,b] conj(psi[a',b]), M = 2^k, 1 <= k <= 6: the raw reduced density matrix of
     /// the qubits `indices` (bit i of a = qubit indices[i]), in double for both precisions.  The state is not changed.
     pub fn qipx_state_reduced_density(s: *mut qip_hip_state, indices: *const u64, k: u32, rho: *mut c_double) -> c_int;
+    /// m[2 (a M + a')] + i m[.. + 1] = sum_b ket[a,b] conj(bra[a',b]), M = 2^k, 1 <= k <= 3: the raw reduced transition matrix
+    /// Tr_rest |ket><bra| of the qubits `indices` (bit i of a = qubit indices[i]), in double for both precisions.  Neither state
+    /// is changed.  Complete when it returns.
+    pub fn qipx_state_transition_matrix(bra: *mut qip_hip_state, ket: *mut qip_hip_state, indices: *const u64, k: u32, m: *mut c_double) -> c_int;
     /// dst[j] <- sum_i (coeffs[2i] + i coeffs[2i+1]) srcs[i][j], 1 <= count <= 16 (0: dst <- 0), in the state's precision; dst may
     /// be any of the sources.  A non-null `norm_sqr` receives sum_j |dst[j]|^2 of the stored values from the same pass.  Complete
     /// when it returns.

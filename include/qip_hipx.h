@@ -249,6 +249,55 @@ int qipx_state_pauli_matrix_elements(qip_hip_state* bra, qip_hip_state* ket, con
  * entry, as by the measurement calls.  The call is ordered after the work queued on the handle and complete when it returns. */
 int qipx_state_reduced_density(qip_hip_state* s, const uint64_t* indices, uint32_t k, double* rho);
 
+/* The two-state counterpart of the call above: the reduced TRANSITION matrix of up to three qubits.  (Purely additive again.)
+ *
+ *   M[a][a'] = sum_b ket[a,b] * conj(bra[a',b]) = Tr_rest |ket><bra|,
+ * rows a and a' the bits of the k qubits, column b all other bits.  <bra| A |ket> = Tr(A M) for EVERY operator A on those qubits,
+ * from one read of the two vectors: what the adjoint method needs for A = dW/dtheta W^H of a parametrised gate W.
+ * `m` holds 2 * 4^k doubles, row-major with M = 2^k: m[2 (a M + a')] and m[2 (a M + a') + 1] are the real and imaginary part of
+ * M[a][a'].  Bit i of a and of a' is the bit of qubit indices[i], the convention of qipx_state_reduced_density; qubit q is index
+ * bit n-1-q.  The value is raw, divided by no norm: tr M = <bra|ket>.  bra == ket is allowed: M is then the reduced density matrix
+ * (up to rounding: no promise is made that the result mirrors bit for bit, nor that it has qipx_state_reduced_density's bits).
+ *
+ * Supported: 1 <= k <= 3, k = n included.  k > 3 is QIP_ERR_UNSUPPORTED with a message that names k.  k = 0, an index >= n, a
+ * repeated index, a null index array, a null `m` and a null handle are QIP_ERR_INVALID: there is no host fall-back.  Handles that
+ * differ in n or dtype are QIP_ERR_INVALID, handles on different devices QIP_ERR_UNSUPPORTED, an unusable handle QIP_ERR_DEVICE,
+ * as by qipx_state_pauli_matrix_elements.  Everything is checked before the first launch: on a refusal neither state nor `m` is
+ * touched.
+ *
+ * Precision and arithmetic.  Products and sums are formed in double for both precisions; f32 amplitudes are widened first.  With
+ * ket[a,b] = xr + i xi and bra[a',b] = yr + i yi a column adds xr yr + xi yi to Re and xi yr - xr yi to Im, each as two fused
+ * multiply-adds into one running sum per part, entry and lane.  There is no Hermitian symmetry: all 4^k entries are formed.
+ *
+ * Kernel.  ONE launch of a kernel of its own (k_transition_small, csrc/qip_kernels.h) plus the fold: the gather skeleton of the
+ * k <= 3 density kernel on two base pointers, each vector read once with non-temporal 16-byte loads, no atomics.  k = 3: 64
+ * complex sums do not fit a lane's registers next to 2 x 8 amplitudes, and the form chosen is THE ENTRIES SPLIT OVER LANES: two
+ * lanes that differ in a lane-id bit that is no position pair up, each keeps the four rows a of one half (all eight a') and forms
+ * them for its own column and for its partner's, whose amplitudes come by 12 wave shuffles of 16 bytes.  No matrix instruction.
+ *
+ * Exact promises.  The same call on the same states returns the same bits (one partial matrix per block in `ket`'s reduction
+ * scratch, folded entry by entry in block order on the device: only 4^k entries cross PCIe).  The kernel works on the qubits'
+ * index positions in ascending order and the host permutes: the result for a permuted index list is the bit-exact row and column
+ * permutation of the result for the sorted list.  An entry all of whose products are zero is exactly zero.  Neither state is
+ * changed.
+ *
+ * Scratch.  At most 4096 blocks of 2 * 4^k doubles (4 MiB at k = 3) plus one matrix, in `ket`'s reduction scratch.
+ *
+ * Error statement.  With S = sum_b |ket[a,b]| |bra[a',b]| <= sqrt(rho_ket[a][a] rho_bra[a'][a']) (Cauchy-Schwarz over two
+ * different rows; rho_x[a][a] = sum_b |x[a,b]|^2) and u = 2^-53, each part of an entry is to first order within c u * 2 S of the
+ * exact sum over the stored amplitudes, c the longest chain of additions a product passes through.  As built: a lane's chain is
+ * its 2^(n-k-20) columns for n - k >= 20 (4096 blocks of 256 lanes), two fused multiply-adds each — at k = 3 the lane meets its
+ * partner's columns too, 2 * 2^(n-23) columns — at most 512 columns at n = 30 for every k; the wave's butterfly 6 (5 at k = 3);
+ * the block's four waves 3; the block fold 4096 / 64 = 64 in a lane, then a tree of 6:
+ *   c <= 2 * 512 + 6 + 3 + 64 + 6 = 1103 at n = 30,
+ * the count of the density call, below 1e-12 / (2 u) = 4500: every entry is within 1e-12 * sqrt(rho_ket[a][a] rho_bra[a'][a'])
+ * of the exact value for every n <= 30 (tests/test_gpu_f2_transition.py holds every entry to that bar).
+ *
+ * Calling contract, as qipx_state_pauli_matrix_elements': both handles are put in the caller's order on entry (option
+ * "tile_relabel" = 3), the call is ordered after the work queued on both handles, runs on `ket`'s stream and is complete when it
+ * returns. */
+int qipx_state_transition_matrix(qip_hip_state* bra, qip_hip_state* ket, const uint64_t* indices, uint32_t k, double* m);
+
 /* Vector arithmetic of resident states: what Lanczos and Krylov iterations need besides qipx_state_apply_pauli_sum.  (Purely
  * additive again.)
  *

@@ -1,7 +1,8 @@
 """rustqip_amd — MI355X-native backend for RustQIP's gate-application hot path.
 
 Public surface (mirrors the reference names for this path):
-  ops      MatrixOp, make_matrix_op, make_sparse_matrix_op, make_swap_op, make_control_op, CircuitError
+  ops      MatrixOp, make_matrix_op, make_sparse_matrix_op, make_swap_op, make_control_op, inverse_op, CircuitError
+  parametric  ParamGate and its constructors (rx, ry, rz, phase, rxx, ryy, rzz, pauli_rotation, generator_gate), gradient_plan
   state    apply_op, apply_op_overwrite, apply_op_row (host-pointer twins; any element type P: complex, real, integer),
            apply_op_device (the same on device slices), HipState (device-resident Complex<P> state), make_op_matrix
   builder  HipBuilder (LocalBuilder's run loop on the GPU)
@@ -9,7 +10,7 @@ Public surface (mirrors the reference names for this path):
 Importing the package loads rustqip_amd/lib/libqip_hip.so and fails loudly if it is missing.
 """
 from . import _ffi  # noqa: F401  (raises ImportError when the HIP library is absent)
-from .ops import (CircuitError, MatrixOp, Representation, algorithmic_bytes, flip_bits, make_control_op,
+from .ops import (CircuitError, MatrixOp, Representation, algorithmic_bytes, flip_bits, inverse_op, make_control_op,
                   make_matrix_op, make_sparse_matrix_op, make_swap_op, validate_op)
 from .state import (HipState, QipHipError, apply_op, apply_op_device, apply_op_overwrite, apply_op_row, device_count,
                     make_op_matrix, set_global_option)
@@ -17,6 +18,7 @@ from .builder import Conditioned, HipBuilder, Measurements, Register, lower_to_m
 from .state import DeviceSlice, HipProgram, expect_pauli_passes, ext_abi_version, pauli_rotation_passes, pauli_sum_passes, von_neumann_entropy
 from .state import krylov_bar, tridiagonal_eigh, tridiagonal_propagator_column
 from . import circuits  # noqa: F401  (workload generators: rustqip_amd.circuits)
+from . import parametric  # noqa: F401  (parametrised gates and the plan of HipState.circuit_gradient)
 from . import replay  # noqa: F401  (flat circuit-replay format)
 
 __all__ = [
@@ -25,4 +27,5 @@ __all__ = [
     "apply_op", "apply_op_device", "apply_op_overwrite", "apply_op_row", "device_count", "make_op_matrix", "set_global_option", "Conditioned",
     "HipBuilder", "Measurements", "Register", "lower_to_matrix_op", "HipProgram", "DeviceSlice", "circuits", "replay", "ext_abi_version", "expect_pauli_passes",
     "pauli_rotation_passes", "pauli_sum_passes", "von_neumann_entropy", "krylov_bar", "tridiagonal_eigh", "tridiagonal_propagator_column",
+    "inverse_op", "parametric",
 ]

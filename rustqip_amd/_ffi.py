@@ -172,6 +172,7 @@ EXT_SIGNATURES = {
     "qipx_pauli_sum_passes": (_int, [_u32, _u64p, _u64p, C.POINTER(C.c_uint8), _u64, _u32, _u64p]),
     "qipx_state_pauli_matrix_elements": (_int, [_statep, _statep, _u64p, _u64p, C.POINTER(C.c_uint8), _u64, _dblp]),
     "qipx_state_reduced_density": (_int, [_statep, _u64p, _u32, _dblp]),
+    "qipx_state_transition_matrix": (_int, [_statep, _statep, _u64p, _u32, _dblp]),
     "qipx_state_linear_combination": (_int, [_statep, C.POINTER(_statep), _dblp, _u32, _dblp]),
     "qipx_state_inner_products": (_int, [C.POINTER(_statep), _u32, _statep, _dblp]),
     "qipx_state_apply_diagonal": (_int, [_statep, _u64p, _u64p, C.POINTER(C.c_uint8), _dblp, _u64, _dbl]),

@@ -7,7 +7,7 @@
 //   qip_jit.hip       the run-time compiler behind qip_jit.h: hiprtc, disk cache, helper processes, resident kernels, plan memo
 //   qip_slice.hip     apply_op on device slices of any element type (qip_hip_apply_op_device): payload cache, kernels, routing
 //   qip_host.hip      host-pointer twins of the reference functions
-//   qip_measure.hip   measurement, sampling, reduced density matrices
+//   qip_measure.hip   measurement, sampling, reduced density and transition matrices
 //   qip_pauli.hip     Pauli-string calls (expectation values, rotations, sums, matrix elements) and vector arithmetic of resident
 //                     states, over qip_pauli_plan.h (terms, planners, pass geometry: plain C++) and qip_pauli_kernels.h; the
 //                     diagonal Pauli sums in one pass, over qip_diag_plan.h (plain C++) and qip_diag_kernels.h
@@ -298,6 +298,9 @@ int tile_apply_single(qip_hip_state* s, const BatchRun& run, const qip_op* op, c
 int prof_begin(qip_hip_state* s, int cls, double bytes, ProfRec* r);
 int prof_end(qip_hip_state* s, ProfRec* r);
 int state_settle(qip_hip_state* s);  // qip_launch.hip: a relabelled state back to the caller's order (one permutation sweep)
+// qip_pauli.hip: how a two-state call meets its handles (the checks; then the caller's order and `other`'s stream drained)
+int pair_meet(const char* what, qip_hip_state* own, qip_hip_state* other);
+int pair_settle(qip_hip_state* own, qip_hip_state* other);
 
 #define STATE_ENTER_NOCHECK(s)                                 \
   if (!(s)) return fail(QIP_ERR_INVALID, "null state handle"); \

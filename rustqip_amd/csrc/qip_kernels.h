@@ -3581,6 +3581,158 @@ __global__ __launch_bounds__(kBlock) void k_density_small(const E* __restrict__ 
     partial[(uint64_t)blockIdx.x * NACC + slot] = ((smem[slot] + smem[NACC + slot]) + smem[2 * NACC + slot]) + smem[3 * NACC + slot];
 }
 
+// ---- two-state reduced matrices (qipx_state_transition_matrix, include/qip_hipx.h) ---------------------------------------
+// M[a][a'] = sum_b ket[a,b] conj(bra[a',b]) over the k <= 3 SORTED positions: the gather skeleton of k_density_small (high
+// positions walked through `ins`, low ones transposed in the wave, B0 and the two columns of a packed element) applied to two
+// base pointers, one non-temporal 16-byte load per element of each vector.  No Hermitian symmetry: all M^2 entries are formed,
+//   Re += xr yr + xi yi,   Im += xi yr - xr yi      (ket[a,b] = xr + i xi, bra[a',b] = yr + i yi),
+// two fused multiply-adds per part, entry and column, in double.  Slot of an entry: 2 (a M + a') and + 1.
+//
+// k = 3 (M = 8): 64 complex sums are 128 doubles, more than a lane can hold next to 2 x 8 amplitudes.  The form chosen is THE
+// ENTRIES SPLIT OVER LANES: the lanes pair up across `fbit`, a lane-id bit that is no position.  A lane keeps the rows a of one
+// half (a < 4 when its fbit is clear, a >= 4 when set) x all eight a' — 64 doubles — and forms them for its own column and for
+// its partner's: it sends the partner the ket rows of the other half and all bra rows (12 elements by shfl_xor) and gets the
+// same back.  Each vector is still read once.  A lane's chain per entry is twice as long as its share of the columns: own
+// column, then the partner's, in that order.
+//
+// The wave adds by a butterfly over the lane bits other than fbit (both lanes of a pair hold the same sum of a stage: the
+// addition commutes), lane 0 stores the rows of the lower half and lane fbit those of the upper; then the block's four waves in
+// wave order, one partial matrix per block.
+struct TransDesc {
+  DensDesc g;     // the geometry of k_density_small
+  uint32_t fbit;  // M = 8: the lane-id bit (as a mask) that pairs the lanes; otherwise 0
+};
+
+template <typename T, bool PACKED, bool B0, int COL, int MA, int M, int MEA, int ME, typename E>
+__device__ __forceinline__ void transition_accumulate(const E (&xa)[MEA], const E (&yb)[ME], double (&re)[MA * M], double (&im)[MA * M]) {
+  double vr[MA], vi[MA], wr[M], wi[M];
+  auto widen = [](const E& e, int ie, double* pr, double* pi) {
+    if constexpr (!PACKED) {
+      pr[ie] = (double)e.x;
+      pi[ie] = (double)e.y;
+    } else if constexpr (B0) {
+      pr[2 * ie] = (double)e.x;
+      pi[2 * ie] = (double)e.y;
+      pr[2 * ie + 1] = (double)e.z;
+      pi[2 * ie + 1] = (double)e.w;
+    } else {
+      pr[ie] = (double)(COL ? e.z : e.x);
+      pi[ie] = (double)(COL ? e.w : e.y);
+    }
+  };
+#pragma unroll
+  for (int ie = 0; ie < MEA; ++ie) widen(xa[ie], ie, vr, vi);
+#pragma unroll
+  for (int ie = 0; ie < ME; ++ie) widen(yb[ie], ie, wr, wi);
+#pragma unroll
+  for (int a = 0; a < MA; ++a)
+#pragma unroll
+    for (int a2 = 0; a2 < M; ++a2) {
+      re[a * M + a2] = __builtin_fma(vi[a], wi[a2], __builtin_fma(vr[a], wr[a2], re[a * M + a2]));
+      im[a * M + a2] = __builtin_fma(-vr[a], wi[a2], __builtin_fma(vi[a], wr[a2], im[a * M + a2]));
+    }
+}
+
+template <typename T, int KE, int KL, bool B0, typename E = amp_t<T>>
+__global__ __launch_bounds__(kBlock) void k_transition_small(const E* __restrict__ ket, const E* __restrict__ bra, Ins ins, TransDesc td,
+                                                             double* __restrict__ partial) {
+  constexpr bool PACKED = !SameT<E, amp_t<T>>::v;
+  static_assert(PACKED || !B0, "the half bit exists in packed elements only");
+  constexpr int KH = KE - KL, ME = 1 << KE, NC = 1 << KH, U = 1 << KL;
+  constexpr int M = B0 ? 2 * ME : ME, NCOL = (PACKED && !B0) ? 2 : 1;
+  constexpr bool SPLIT = M == 8;
+  constexpr int MA = SPLIT ? M / 2 : M, MEA = SPLIT ? ME / 2 : ME, NOUT = 2 * M * M;
+  static_assert(M <= 8, "k <= 3");
+  __shared__ double smem[(kBlock / 64) * NOUT];
+  const DensDesc& d = td.g;
+  double re[MA * M], im[MA * M];
+#pragma unroll
+  for (int p = 0; p < MA * M; ++p) re[p] = im[p] = 0.0;
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const bool hi = SPLIT && (lane & td.fbit) != 0u;
+  const uint64_t nwaves = (uint64_t)gridDim.x * (kBlock / 64);
+  for (uint64_t row0 = ((uint64_t)blockIdx.x * (kBlock / 64) + wv) * U; row0 < d.nrows; row0 += nwaves * U) {
+    E x[U][NC], y[U][NC];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint64_t row = row0 + (uint64_t)u;
+      const bool valid = row < d.nrows && lane < d.nlane;
+      const uint64_t base = insert_bits<KH>((row << 6) | lane, ins);
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        E e = {}, f = {};
+        if (valid) {
+          e = __builtin_nontemporal_load(ket + (base | d.coff[c]));
+          f = __builtin_nontemporal_load(bra + (base | d.coff[c]));
+        }
+        x[u][c] = e;
+        y[u][c] = f;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < KL; ++i) {
+      const bool up = (lane >> d.lpos[i]) & 1u;
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if ((u >> i) & 1) continue;
+        const int u1 = u | (1 << i);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          const E e0 = x[u][c], e1 = x[u1][c];
+          const E got = shfl_xor_e<E>(up ? e0 : e1, 1 << d.lpos[i]);
+          x[u][c] = up ? got : e0;
+          x[u1][c] = up ? e1 : got;
+          const E f0 = y[u][c], f1 = y[u1][c];
+          const E fgot = shfl_xor_e<E>(up ? f0 : f1, 1 << d.lpos[i]);
+          y[u][c] = up ? fgot : f0;
+          y[u1][c] = up ? f1 : fgot;
+        }
+      }
+    }
+    E xe[ME], ye[ME];  // by element row ie = (c << KL) | u
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        xe[(c << KL) | u] = x[u][c];
+        ye[(c << KL) | u] = y[u][c];
+      }
+    if constexpr (!SPLIT) {
+      transition_accumulate<T, PACKED, B0, 0, MA, M, MEA, ME, E>(xe, ye, re, im);
+      if constexpr (NCOL == 2) transition_accumulate<T, PACKED, B0, 1, MA, M, MEA, ME, E>(xe, ye, re, im);
+    } else {
+      E xo[MEA], gx[MEA], gy[ME];  // the ket rows of the lane's half: its own column's, then the partner's with the partner's bra rows
+#pragma unroll
+      for (int j = 0; j < MEA; ++j) {
+        xo[j] = hi ? xe[MEA + j] : xe[j];
+        gx[j] = shfl_xor_e<E>(hi ? xe[j] : xe[MEA + j], (int)td.fbit);
+      }
+#pragma unroll
+      for (int j = 0; j < ME; ++j) gy[j] = shfl_xor_e<E>(ye[j], (int)td.fbit);
+      transition_accumulate<T, PACKED, B0, 0, MA, M, MEA, ME, E>(xo, ye, re, im);
+      if constexpr (NCOL == 2) transition_accumulate<T, PACKED, B0, 1, MA, M, MEA, ME, E>(xo, ye, re, im);
+      transition_accumulate<T, PACKED, B0, 0, MA, M, MEA, ME, E>(gx, gy, re, im);
+      if constexpr (NCOL == 2) transition_accumulate<T, PACKED, B0, 1, MA, M, MEA, ME, E>(gx, gy, re, im);
+    }
+  }
+  const uint32_t skip = SPLIT ? td.fbit : 0u;
+  auto fold = [&](double v, int local) {  // local = 2 (a_local M + a') (+ 1)
+#pragma unroll
+    for (uint32_t o = 32; o > 0; o >>= 1)
+      if (o != skip) v += __shfl_xor(v, (int)o, 64);
+    if (lane == 0) smem[wv * NOUT + local] = v;
+    if (SPLIT && lane == skip) smem[wv * NOUT + MA * M * 2 + local] = v;
+  };
+#pragma unroll
+  for (int p = 0; p < MA * M; ++p) {
+    fold(re[p], 2 * p);
+    fold(im[p], 2 * p + 1);
+  }
+  __syncthreads();
+  for (int slot = threadIdx.x; slot < NOUT; slot += kBlock)
+    partial[(uint64_t)blockIdx.x * NOUT + slot] = ((smem[slot] + smem[NOUT + slot]) + smem[2 * NOUT + slot]) + smem[3 * NOUT + slot];
+}
+
 // k = 4 .. 6 — f64 matrix cores.  With Psi a 2^k x (columns) matrix, rho = Psi Psi^H is a Hermitian rank update.  The operand
 // layouts of v_mfma_f64_16x16x4_f64 are A[lane & 15][lane >> 4] and B[lane >> 4][lane & 15]: ONE register holding
 // X[row = lane & 15][column = lane >> 4] of a 16-row block of Psi is the A operand X and the B operand X^T at once, so Xr and Xi

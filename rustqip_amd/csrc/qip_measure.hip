@@ -814,6 +814,126 @@ extern "C" int qipx_state_reduced_density(qip_hip_state* s, const uint64_t* indi
   return QIP_OK;
 } QIP_CATCH_ALL
 
+// ---- two-state reduced matrices (include/qip_hipx.h) ----------------------------------------------------------------------
+//   meet    the two handles as pauli_matrix_elements meets its own (pair_meet, pair_settle), every refusal before anything is queued
+//   launch  k_transition_small on the sorted positions, the geometry of density_small_t; one partial matrix of 2 * 4^k doubles per
+//           block in ket's d_partial
+//   fold    k_sum_partials in block order on the device; the host moves the sorted entries to the caller's bit order
+template <typename T, int KE, int KL, bool B0>
+static void transition_launch(qip_hip_state* ket, const qip_hip_state* bra, const DensityGeom& g, unsigned gx, const Ins& ins, const TransDesc& d) {
+  if constexpr (std::is_same<T, float>::value) {
+    if (g.packed) {
+      hipLaunchKernelGGL((k_transition_small<float, KE, KL, B0, f32x4>), dim3(gx), dim3(kBlock), 0, ket->stream, (const f32x4*)ket->cur,
+                         (const f32x4*)bra->cur, ins, d, ket->d_partial);
+      return;
+    }
+  }
+  if constexpr (!B0)
+    hipLaunchKernelGGL((k_transition_small<T, KE, KL, false>), dim3(gx), dim3(kBlock), 0, ket->stream, (const amp_t<T>*)ket->cur,
+                       (const amp_t<T>*)bra->cur, ins, d, ket->d_partial);
+}
+
+template <typename T, int KE, bool B0>
+static void transition_kl(qip_hip_state* ket, const qip_hip_state* bra, const DensityGeom& g, uint32_t kl, unsigned gx, const Ins& ins, const TransDesc& d) {
+  switch (kl) {
+    case 0: transition_launch<T, KE, 0, B0>(ket, bra, g, gx, ins, d); break;
+    case 1: if constexpr (KE >= 1) transition_launch<T, KE, 1, B0>(ket, bra, g, gx, ins, d); break;
+    case 2: if constexpr (KE >= 2) transition_launch<T, KE, 2, B0>(ket, bra, g, gx, ins, d); break;
+    default: if constexpr (KE >= 3) transition_launch<T, KE, 3, B0>(ket, bra, g, gx, ins, d); break;
+  }
+}
+
+// `full`: the matrix in sorted bit order, full[2 (a M + a')] and full[.. + 1]
+template <typename T>
+static int transition_t(qip_hip_state* ket, const qip_hip_state* bra, const std::vector<uint32_t>& sorted, std::vector<double>* full) {
+  const DensityGeom g = density_geom<T>(ket, sorted);
+  const uint32_t k = (uint32_t)sorted.size(), ke = (uint32_t)g.pe.size(), M = 1u << k;
+  TransDesc d;
+  memset(&d, 0, sizeof d);
+  uint32_t kl = 0, lanebits = 0;
+  std::vector<uint32_t> high;
+  for (uint32_t p : g.pe) {
+    if (p < 6) {
+      d.g.lpos[kl++] = p;
+      lanebits |= 1u << p;
+    } else {
+      high.push_back(p);
+    }
+  }
+  if (k == 3) d.fbit = (~lanebits) & (lanebits + 1u);  // the lowest lane-id bit that is no position (at most three are)
+  const uint32_t kh = ke - kl;
+  for (uint32_t c = 0; c < (1u << kh); ++c)
+    for (uint32_t i = 0; i < kh; ++i)
+      if ((c >> i) & 1u) d.g.coff[c] |= 1ull << high[i];
+  const uint64_t items = 1ull << (g.ne - kh);
+  d.g.nrows = std::max<uint64_t>(items >> 6, 1);
+  d.g.nlane = (uint32_t)std::min<uint64_t>(items, 64);
+  const unsigned gx = (unsigned)std::min<uint64_t>(std::max<uint64_t>(d.g.nrows / ((uint64_t)(1u << kl) * (kBlock / 64)), 1), kDensitySmallBlocks);
+  const size_t nout = 2 * (size_t)M * M;
+  QCHK(ensure_partial(ket, (size_t)gx * nout + nout));
+  const Ins ins = make_ins(high, 0);
+  if (g.b0) {
+    if constexpr (std::is_same<T, float>::value) {
+      switch (ke) {
+        case 0: transition_kl<float, 0, true>(ket, bra, g, kl, gx, ins, d); break;
+        case 1: transition_kl<float, 1, true>(ket, bra, g, kl, gx, ins, d); break;
+        default: transition_kl<float, 2, true>(ket, bra, g, kl, gx, ins, d); break;
+      }
+    }
+  } else {
+    switch (ke) {
+      case 1: transition_kl<T, 1, false>(ket, bra, g, kl, gx, ins, d); break;
+      case 2: transition_kl<T, 2, false>(ket, bra, g, kl, gx, ins, d); break;
+      default: transition_kl<T, 3, false>(ket, bra, g, kl, gx, ins, d); break;
+    }
+  }
+  HIPCHK(hipGetLastError());
+  const double* res = ket->d_partial;
+  if (gx > 1) {
+    hipLaunchKernelGGL((k_sum_partials<64>), dim3(grid_for(nout, kBlock / 64)), dim3(kBlock), 0, ket->stream, ket->d_partial, (uint32_t)gx,
+                       (uint64_t)nout, ket->d_partial + (size_t)gx * nout);
+    HIPCHK(hipGetLastError());
+    res = ket->d_partial + (size_t)gx * nout;
+  }
+  full->resize(nout);
+  HIPCHK(hipMemcpyAsync(full->data(), res, nout * sizeof(double), hipMemcpyDeviceToHost, ket->stream));
+  HIPCHK(hipStreamSynchronize(ket->stream));
+  return QIP_OK;
+}
+
+extern "C" int qipx_state_transition_matrix(qip_hip_state* bra, qip_hip_state* ket, const uint64_t* indices, uint32_t k, double* m) try {
+  STATE_ENTER_RAW(ket);
+  QCHK(pair_meet("transition_matrix", ket, bra));
+  if (!m) return fail(QIP_ERR_INVALID, "transition_matrix: null output");
+  MeasDesc md;
+  std::vector<uint32_t> pos;
+  QCHK(check_measure_indices(ket, indices, k, &md, &pos));
+  if (k > 3) return fail(QIP_ERR_UNSUPPORTED, "transition_matrix over k = %u qubits (at most 3)", k);
+  QCHK(pair_settle(ket, bra));
+  // bit j of the kernel's row index = the j-th lowest position = bit perm[j] of the caller's
+  std::vector<uint32_t> perm(k);
+  for (uint32_t i = 0; i < k; ++i) perm[i] = i;
+  std::sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return pos[a] < pos[b]; });
+  std::vector<uint32_t> sorted(k);
+  for (uint32_t j = 0; j < k; ++j) sorted[j] = pos[perm[j]];
+  std::vector<double> full;
+  QCHK(ket->dtype == QIP_C64 ? transition_t<double>(ket, bra, sorted, &full) : transition_t<float>(ket, bra, sorted, &full));
+  const uint32_t M = 1u << k;
+  uint32_t to_caller[8];
+  for (uint32_t a = 0; a < M; ++a) {
+    uint32_t c = 0;
+    for (uint32_t j = 0; j < k; ++j) c |= ((a >> j) & 1u) << perm[j];
+    to_caller[a] = c;
+  }
+  for (uint32_t a = 0; a < M; ++a)
+    for (uint32_t a2 = 0; a2 < M; ++a2) {
+      const size_t o = 2 * ((size_t)to_caller[a] * M + to_caller[a2]), i = 2 * ((size_t)a * M + a2);
+      m[o] = full[i];
+      m[o + 1] = full[i + 1];
+    }
+  return QIP_OK;
+} QIP_CATCH_ALL
+
 extern "C" int qip_hip_state_measure(qip_hip_state* s, const uint64_t* indices, uint32_t k,
                                      int64_t forced, double rand_u01, uint64_t* measured, double* prob) try {
   STATE_ENTER(s);

@@ -360,7 +360,7 @@ extern "C" int qipx_state_expect_diagonal(qip_hip_state* s, const uint64_t* term
 //   meet    the two handles as copy_from and max_abs_diff meet theirs (pair_meet: the checks; pair_settle: the caller's order and
 //           the other handle's stream drained), everything that can refuse the call before anything is queued
 // Both calls are complete when they return.
-static int pair_meet(const char* what, qip_hip_state* own, qip_hip_state* other) {
+int pair_meet(const char* what, qip_hip_state* own, qip_hip_state* other) {
   if (!other) return fail(QIP_ERR_INVALID, "%s: null state handle", what);
   if (other->poisoned) return fail(QIP_ERR_DEVICE, "%s: the other state is unusable: %s", what, other->poison_msg.c_str());
   if (own->n != other->n || own->dtype != other->dtype) return fail(QIP_ERR_INVALID, "%s: states differ in size or precision", what);
@@ -369,7 +369,7 @@ static int pair_meet(const char* what, qip_hip_state* own, qip_hip_state* other)
 }
 
 // both in the caller's order, and everything queued on `other` has landed: the work then runs on `own`'s stream
-static int pair_settle(qip_hip_state* own, qip_hip_state* other) {
+int pair_settle(qip_hip_state* own, qip_hip_state* other) {
   if (!own->layout.empty()) QCHK(state_settle(own));
   if (other != own) {
     if (!other->layout.empty()) QCHK(state_settle(other));

@@ -480,6 +480,18 @@ template <typename P> class HipState {
     for (size_t t = 0; t < out.size(); ++t) out[t] = {flat[2 * t], flat[2 * t + 1]};
     return out;
   }
+  /// The raw reduced transition matrix of up to three qubits (qip_hipx.h), *this the bra, row-major with M = 2^k:
+  /// out[a * M + a'] = sum_b ket[a,b] conj((*this)[a',b]), bit i of a = qubit indices[i]; <*this| A |ket> = Tr(A out) for every
+  /// operator A on those qubits.  `ket` may be *this.  Neither state is changed.
+  std::vector<std::complex<double>> transition_matrix(HipState& ket, const std::vector<size_t>& indices) {
+    std::vector<uint64_t> idx(indices.begin(), indices.end());
+    const size_t m = size_t(1) << std::min<size_t>(idx.size(), 3);
+    std::vector<double> flat(2 * m * m);
+    check(qipx_state_transition_matrix(h_, ket.h_, idx.data(), (uint32_t)idx.size(), flat.data()));
+    std::vector<std::complex<double>> out(m * m);
+    for (size_t t = 0; t < out.size(); ++t) out[t] = {flat[2 * t], flat[2 * t + 1]};
+    return out;
+  }
   /// *this[j] <- sum_i coeffs[i] * (*srcs[i])[j] in one pass (qip_hipx.h): up to 16 states of the same n, precision and device,
   /// *this allowed among them; no sources: *this <- 0.  With `norm_sqr` the pass also returns sum_j |(*this)[j]|^2 of the stored
   /// amplitudes.  Complete when it returns.

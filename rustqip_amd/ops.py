@@ -223,6 +223,37 @@ def make_control_op(c_indices: Sequence[int], op: MatrixOp) -> MatrixOp:
     return MatrixOp("Control", c + list(op.indices), n_controls=len(c), inner=op)
 
 
+def inverse_op(op: MatrixOp) -> MatrixOp:
+    """The op that undoes a unitary `op`.  Matrix: the conjugate transpose of the data; SparseMatrix: the conjugate transpose
+    of the rows (entry (r, c, v) becomes (c, r, conj v), every row's columns ascending); Swap: itself; Control: the control of
+    the inverse.  Host bookkeeping only: the op is taken to be unitary and is not checked (a sparse op whose transpose has an
+    empty row is not unitary and is refused)."""
+    if op.kind == "Matrix":
+        side = 1 << len(op.indices)
+        data = np.asarray(op.data, dtype=np.complex128)
+        if data.size != side * side:
+            raise CircuitError(f"Matrix data has {data.size} entries versus expected 2^2*{len(op.indices)}")
+        return MatrixOp("Matrix", list(op.indices), data=np.ascontiguousarray(data.reshape(side, side).conj().T).ravel())
+    if op.kind == "SparseMatrix":
+        rows: List[List[Tuple[int, complex]]] = [[] for _ in op.rows]
+        for r, row in enumerate(op.rows):
+            for c, v in row:
+                if not 0 <= c < len(rows):
+                    raise CircuitError(f"sparse column {c} outside the op's {len(rows)} rows")
+                rows[c].append((r, complex(v).conjugate()))
+        for c, row in enumerate(rows):
+            if not row:
+                raise CircuitError(f"the op is not unitary: column {c} of its sparse matrix is empty")
+        return MatrixOp("SparseMatrix", list(op.indices), rows=rows)
+    if op.kind == "Swap":
+        return MatrixOp("Swap", list(op.indices), half=op.half)
+    if op.kind == "Control":
+        if op.inner is None:
+            raise CircuitError("Control op without inner op")
+        return MatrixOp("Control", list(op.indices), n_controls=op.n_controls, inner=inverse_op(op.inner))
+    raise CircuitError(f"unknown op kind {op.kind!r}")
+
+
 def flatten(op: MatrixOp):
     """(control qubits, innermost op, target qubits) with nested Controls accumulated the way
     sum_for_control_iterator does (ops.rs:150-154); only the OUTER index list is used (matrix_ops.rs:108)."""

@@ -677,6 +677,86 @@ class HipState:
             work.apply_pauli_rotations([rot_terms[k]], [-a[k]])
         return float(energy), grad
 
+    def transition_matrix(self, ket: "HipState", indices: Sequence[int]) -> np.ndarray:
+        """complex128[2^k, 2^k]: M[a, a'] = sum_b ket[a,b] conj(self[a',b]) = Tr_rest |ket><self|, the reduced transition matrix of
+        the k <= 3 qubits `indices` (include/qip_hipx.h); `self` is the bra, as in pauli_matrix_elements.  <self| A |ket> =
+        trace(A @ M) for every operator A on those qubits, from one read of the two vectors.  Bit i of a and of a' is the bit
+        of qubit indices[i], as in reduced_density_matrix.  Raw (divided by no norm), in double for both precisions; `ket` may be
+        `self`.  Neither state is changed.  A malformed index list raises CircuitError before the library is called, k > 3 is the
+        library's refusal (QipHipError).  `self.transition_passes` counts the calls that ran (one kernel pass each)."""
+        self._partner(ket, "transition_matrix")
+        try:
+            indices = [int(q) for q in indices]
+        except (TypeError, ValueError):
+            raise CircuitError(f"transition_matrix: not a list of qubit indices: {indices!r}") from None
+        k = len(indices)
+        if k == 0 or len(set(indices)) != k or min(indices) < 0 or max(indices) >= self.n:
+            raise CircuitError(f"transition_matrix: {indices} is not a list of distinct qubits of a {self.n}-qubit state")
+        side = 1 << min(k, 3)
+        out = np.zeros((side, side), dtype=np.complex128)
+        _check(_ffi.lib.qipx_state_transition_matrix(self._h, ket._h, _u64_array(indices), k,
+                                                     out.view(np.float64).ctypes.data_as(C.POINTER(C.c_double))))
+        self.transition_passes = getattr(self, "transition_passes", 0) + 1
+        return out
+
+    def circuit_gradient(self, circuit, params, obs_terms, obs_coeffs, work: "HipState") -> Tuple[float, np.ndarray]:
+        """(E, float64[len(params)]): the energy E = <psi_T| H |psi_T> and its gradient with respect to `params`, for psi_T = the
+        circuit applied to psi_0 and H = sum_t obs_coeffs[t] * obs_terms[t] with real coefficients.  `circuit` is a list whose
+        items are a MatrixOp (fixed, taken to be unitary, any kind and size) or a pair (parametric.ParamGate, p), p an index into
+        `params`; a parameter may be used by several gates (their contributions add), one used by none gets 0.  `self` holds
+        psi_0; `work` is a second state of the same n, precision and device whose content is overwritten.
+
+        The adjoint method on blocks (parametric.gradient_plan is the plan this executes): the lowered circuit forward in one
+        apply_ops, lambda = H psi_T into `work`, E = Re <lambda|psi_T>; then per block, the last first: one
+        work.transition_matrix(self, qubits) per pass, dE/dtheta_g = 2 Re trace(A_g M_g) for every parametrised gate g of the
+        pass (A_g = dW_g W_g^H, M_g the pass's matrix traced down to g's qubits on the host), and the block undone on both
+        states by one apply_ops of the inverses each.  One read of both vectors per pass, against two runs of the circuit and
+        an expectation per parameter for parameter shift.
+
+        Refused with CircuitError before anything is queued: a parametrised gate on more than 3 qubits (controls included), a
+        parameter index out of range, a non-finite parameter or coefficient, `work` being `self`, malformed terms or ops.
+
+        On return `self` holds psi_0 again up to the rounding of the gates forward and back (it is not restored from a copy),
+        and `work` holds H psi_T pulled back through the circuit in the same way."""
+        from .ops import inverse_op, validate_op
+        from .parametric import circuit_items, gradient_plan, reduce_transition
+
+        circuit, obs_terms = list(circuit), list(obs_terms)
+        theta = np.asarray(params, dtype=np.float64).reshape(-1)
+        c = np.asarray(obs_coeffs, dtype=np.float64).reshape(-1)
+        if len(c) != len(obs_terms):
+            raise CircuitError(f"{len(obs_terms)} terms but {len(c)} coefficients")
+        if not np.all(np.isfinite(theta)) or not np.all(np.isfinite(c)):
+            raise CircuitError("a parameter or a coefficient is not finite")
+        items = circuit_items(circuit)
+        for i, (_, p, _) in enumerate(items):
+            if p is not None and p >= len(theta):
+                raise CircuitError(f"circuit item {i}: parameter index {p} but {len(theta)} parameters")
+        plan = gradient_plan(circuit)
+        self._partner(work, "circuit_gradient")
+        if work is self or work._h.value == self._h.value:
+            raise CircuitError("circuit_gradient: the work state is the state itself")
+        pauli_sum_passes(self.n, obs_terms)  # (malformed terms raise here, before anything is queued)
+        lowered = [g if p is None else g.lower(theta[p]) for g, p, _ in items]
+        for op in lowered:
+            validate_op(self.n, op, self.dtype)
+        inverses = [inverse_op(op) for op in lowered]
+        if lowered:
+            self.apply_ops(lowered)
+        work.apply_pauli_sum(self, obs_terms, c)
+        energy = work.inner(self).real
+        grad = np.zeros(len(theta), dtype=np.float64)
+        for block in plan:
+            for ps in block["passes"]:
+                m = work.transition_matrix(self, ps["qubits"])
+                for i in ps["gates"]:
+                    gate, p, qubits = items[i]
+                    grad[p] += 2.0 * float(np.trace(gate.a_matrix(theta[p]) @ reduce_transition(m, ps["qubits"], qubits)).real)
+            undo = [inverses[i] for i in reversed(block["gates"])]
+            self.apply_ops(undo)
+            work.apply_ops(undo)
+        return float(energy), grad
+
     # -- vector arithmetic and Krylov solvers (include/qip_hipx.h) -----------------------------------------------------
     def _handles(self, states, what: str):
         states = list(states)
