@@ -133,4 +133,29 @@ extern "C" {
         count: u64,
         moments: *mut c_double,
     ) -> c_int;
+    /// |x>|y> -> w(x) |x>|y'>: y' = y ^ values[x] (`mode` 0, QIPX_FN_XOR) or (y + values[x]) mod 2^k (`mode` 1, QIPX_FN_ADD), bit i of
+    /// x / y = qubit in_qubits[i] / out_qubits[i]; w = 1 (null `phases`: amplitudes are moved with their bits) or
+    /// (cos phases[x], sin phases[x]).  2^m entries; k = 0: null `values`, a phase by table.  In place, one pass per six out
+    /// positions outside the six low index bits (ADD: at most six); queued on the handle's stream, returns without waiting.
+    pub fn qipx_state_apply_function(
+        s: *mut qip_hip_state,
+        in_qubits: *const u64,
+        m: u32,
+        out_qubits: *const u64,
+        k: u32,
+        mode: c_int,
+        values: *const u64,
+        phases: *const c_double,
+    ) -> c_int;
+    /// The number of passes over the vector that `qipx_state_apply_function` makes on `n` qubits, after the same checks of the
+    /// registers and the mode.  Host-only.
+    pub fn qipx_function_passes(
+        n: u32,
+        in_qubits: *const u64,
+        m: u32,
+        out_qubits: *const u64,
+        k: u32,
+        mode: c_int,
+        passes: *mut u32,
+    ) -> c_int;
 }

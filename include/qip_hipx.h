@@ -424,6 +424,61 @@ int qipx_state_apply_diagonal(qip_hip_state* s, const uint64_t* term_start, cons
 int qipx_state_expect_diagonal(qip_hip_state* s, const uint64_t* term_start, const uint64_t* qubits, const uint8_t* paulis,
                                const double* coeffs, uint64_t count, double* moments /* [2] */);
 
+/* Classical functions between qubit registers in one pass: |x>|y> -> e^{i phi(x)} |x>|y (+) f(x)>, the oracles of Grover and
+ * amplitude amplification, the arithmetic of Shor-type circuits with a classical base and modulus, comparators, table look-ups
+ * and QROM loads, without Toffoli networks and without ancilla qubits.  (Purely additive again.)
+ *
+ * Registers.  in_qubits[0..m) and out_qubits[0..k) are disjoint lists of distinct qubits (qubit q = index bit n-1-q); bit i of the
+ * register value x / y is the bit of qubit in_qubits[i] / out_qubits[i] (LSB first, as in measure_probs and
+ * qipx_state_reduced_density).  For every basis index j with in-register value x and out-register value y, every other bit
+ * untouched,
+ *   new[j with y replaced by y'] = w(x) * old[j],
+ *   QIPX_FN_XOR:  y' = y ^ values[x]            QIPX_FN_ADD:  y' = (y + values[x]) mod 2^k.
+ * `values` and `phases` hold 2^m entries.  m = 0 is a constant (an X mask, an increment by a constant).  k = 0 requires
+ * values == NULL and a non-NULL `phases`: a phase by table on a register (a Grover oracle for any marked set, any diagonal
+ * function of up to 2^m distinct values).  A control needs no parameter of its own: it is an in-register bit with values[x] = 0
+ * where it reads 0.  m <= 24, k <= 32, m + k <= n.
+ *
+ * Arithmetic.  phases == NULL: w = 1, amplitudes are moved, not multiplied; the result carries the input's bits exactly, signed
+ * zeros and non-finite values included.  Otherwise w(x) = (cos phases[x], sin phases[x]), evaluated by the host's libm in double and
+ * rounded once to the state's precision; it is applied as ONE complex product in the state's precision (re = wr ar - wi ai,
+ * im = wr ai + wi ar; a compiler may contract a product into the sum).  An entry that rounds to exactly (1, 0) is not multiplied:
+ * that amplitude is moved with its bits.  Against the exact product the error of an amplitude is at most 8 u |psi_j|, u = 2^-53 or
+ * 2^-24 (2 u for the rounded table entry, sqrt(5) u for the product, the rest for libm).
+ *
+ * Cost.  An amplitude only moves among the 2^k indices that share its x and its other bits, so a tile made of a wave row (index
+ * bits 0..5) and the out register's positions outside it is closed under the map.  A block stages such tiles in LDS, 2^(6+h)
+ * amplitudes for h out positions outside the row, loaded and stored in place as whole rows: every amplitude is read once and
+ * written once per pass, no atomics, no second buffer.  A pass holds at most 6 out positions outside the six low index bits
+ * (64 KiB of Complex<f64> per block).  QIPX_FN_XOR over more splits into ceil(h / 6) passes over disjoint subsets of the out bits,
+ * each a complete XOR on its subset.  QIPX_FN_ADD does not split (carries cross): an out register with MORE THAN 6 positions
+ * outside the six low index bits is refused in that mode.  Out bits inside the row cost nothing.  The table is one 32-bit word
+ * per entry and pass plus, with phases, one amplitude per entry; it lives in a device buffer of the handle (the one of
+ * qipx_state_apply_diagonal), grown on demand and freed with it.  tools/bench_function.py measures the passes against a gate pass
+ * and against the same maps as SparseMatrix ops and Toffoli networks.
+ *
+ * Calling contract.  The state is changed in place; the launches are queued on the handle's stream and the call returns without
+ * waiting (a relabelled state, option "tile_relabel" = 3, is put back in the caller's order first; an unusable one is refused with
+ * QIP_ERR_DEVICE).  The caller's arrays may be freed or rewritten as soon as the call returns: the table travels through a pinned
+ * buffer of the handle and its upload is stream-ordered, exactly as for qipx_state_apply_diagonal.
+ * Each of these is QIP_ERR_INVALID with a message, before anything is queued, the state untouched: a null handle (there is no host
+ * fall-back); a qubit >= n ("out of range"), listed twice ("repeated") or in both registers; an unknown mode; m > 24 or k > 32; a
+ * null qubit array of a non-empty register; k > 0 with values == NULL ("null value array"); k = 0 with values or without phases;
+ * values[x] >= 2^k ("does not fit"); a non-finite phase; QIPX_FN_ADD beyond the limit above.
+ *
+ * qipx_function_passes is host-only, like qipx_pauli_rotation_passes: the number of passes over the vector that the call above
+ * makes on n qubits, after the same checks of the registers and the mode with the same messages.  It needs no device.
+ *
+ * Out of scope: general in-place bijections of a register that do not preserve x (addition or multiplication modulo a QUANTUM
+ * register's value, the reference's add_mod / times_mod); recording the call into programs / hipGraph, the sharded state, the
+ * builder, replay and QASM; the C++ mirror.  There is no option, and the launches are not a kernel class of the profile. */
+#define QIPX_FN_XOR 0
+#define QIPX_FN_ADD 1
+int qipx_state_apply_function(qip_hip_state* s, const uint64_t* in_qubits, uint32_t m, const uint64_t* out_qubits, uint32_t k, int mode,
+                              const uint64_t* values, const double* phases);
+int qipx_function_passes(uint32_t n, const uint64_t* in_qubits, uint32_t m, const uint64_t* out_qubits, uint32_t k, int mode,
+                         uint32_t* passes);
+
 #ifdef __cplusplus
 }
 #endif

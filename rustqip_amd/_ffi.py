@@ -177,6 +177,8 @@ EXT_SIGNATURES = {
     "qipx_state_inner_products": (_int, [C.POINTER(_statep), _u32, _statep, _dblp]),
     "qipx_state_apply_diagonal": (_int, [_statep, _u64p, _u64p, C.POINTER(C.c_uint8), _dblp, _u64, _dbl]),
     "qipx_state_expect_diagonal": (_int, [_statep, _u64p, _u64p, C.POINTER(C.c_uint8), _dblp, _u64, _dblp]),
+    "qipx_state_apply_function": (_int, [_statep, _u64p, _u32, _u64p, _u32, _int, _u64p, _dblp]),
+    "qipx_function_passes": (_int, [_u32, _u64p, _u32, _u64p, _u32, _int, C.POINTER(C.c_uint32)]),
 }
 
 

@@ -11,6 +11,8 @@
 //   qip_pauli.hip     Pauli-string calls (expectation values, rotations, sums, matrix elements) and vector arithmetic of resident
 //                     states, over qip_pauli_plan.h (terms, planners, pass geometry: plain C++) and qip_pauli_kernels.h; the
 //                     diagonal Pauli sums in one pass, over qip_diag_plan.h (plain C++) and qip_diag_kernels.h
+//   qip_function.hip  classical functions between qubit registers (qipx_state_apply_function), over qip_function_plan.h (plain
+//                     C++) and qip_function_kernels.h; its table travels through qip_pauli.hip's table buffer
 //   qip_dist.hip      the sharded state (planner, pack sweep, exchange)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -181,7 +183,8 @@ struct qip_hip_state {
   int64_t expect_group = kExpectGroupDefault;  // option "expect_group": most terms of qipx_state_expect_pauli that share a pass
   int64_t rotate_group = kRotateGroupDefault;  // option "rotate_group": most terms of qipx_state_apply_pauli_rotations that share a pass
   int64_t sum_group = kSumGroupDefault;  // option "sum_group": most terms of qipx_state_apply_pauli_sum that share a pass
-  // qipx_state_apply_diagonal / expect_diagonal (qip_pauli.hip): the term table on the device and TWO pinned host copies used in
+  // The table buffer (qip_pauli.hip: table_stage / table_commit) of qipx_state_apply_diagonal / expect_diagonal and
+  // qipx_state_apply_function: the call's table on the device and TWO pinned host copies used in
   // turn to feed its stream-ordered upload, each with the event recorded behind its last upload (a host copy is rewritten only
   // once that event has passed: a call waits for the upload of the call before the previous one, never for the previous call)
   void* d_diag = nullptr;
@@ -301,6 +304,10 @@ int state_settle(qip_hip_state* s);  // qip_launch.hip: a relabelled state back 
 // qip_pauli.hip: how a two-state call meets its handles (the checks; then the caller's order and `other`'s stream drained)
 int pair_meet(const char* what, qip_hip_state* own, qip_hip_state* other);
 int pair_settle(qip_hip_state* own, qip_hip_state* other);
+// qip_pauli.hip: the handle's table buffer.  table_stage: room for `bytes` and the pinned copy whose turn it is, free to be
+// written; table_commit: that copy's stream-ordered upload to s->d_diag
+int table_stage(qip_hip_state* s, size_t bytes, char** host, uint32_t* turn);
+int table_commit(qip_hip_state* s, uint32_t turn, size_t bytes);
 
 #define STATE_ENTER_NOCHECK(s)                                 \
   if (!(s)) return fail(QIP_ERR_INVALID, "null state handle"); \

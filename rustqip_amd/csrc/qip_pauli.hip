@@ -260,10 +260,10 @@ static int diag_check(const char* what, qip_hip_state* s, const uint64_t* term_s
   return QIP_OK;
 }
 
-static int diag_upload(qip_hip_state* s, const DiagPlan& plan, const DiagGeom& g, DiagSumDesc* d) {
-  const size_t nterms = plan.terms.size(), ngroups = plan.group_mask.size();
-  const size_t off_start = nterms * sizeof(DiagTerm), off_mask = off_start + (ngroups + 1) * sizeof(uint32_t);
-  const size_t bytes = off_mask + ngroups * sizeof(uint32_t);
+// The handle's table buffer (qip_internal.h: d_diag, h_diag): what every call that ships a table built on the host shares — the
+// diagonal sums here and qipx_state_apply_function (qip_function.hip).  table_stage: room for `bytes` (grown after waiting for the
+// stream), the pinned copy whose turn it is, free to be written; table_commit: its upload queued, the event behind it recorded.
+int table_stage(qip_hip_state* s, size_t bytes, char** host, uint32_t* turn_out) {
   if (bytes > s->diag_cap) {
     HIPCHK(hipStreamSynchronize(s->stream));  // (a kernel may still read the old table, a copy the old host buffers)
     if (s->d_diag) HIPCHK(hipFree(s->d_diag));
@@ -282,12 +282,28 @@ static int diag_upload(qip_hip_state* s, const DiagPlan& plan, const DiagGeom& g
   s->diag_turn ^= 1u;
   if (s->diag_uploaded[turn]) HIPCHK(hipEventSynchronize(s->diag_uploaded[turn]));  // this copy's last upload has left it
   else HIPCHK(hipEventCreateWithFlags(&s->diag_uploaded[turn], hipEventDisableTiming));
-  char* h = (char*)s->h_diag[turn];
+  *host = (char*)s->h_diag[turn];
+  *turn_out = turn;
+  return QIP_OK;
+}
+
+int table_commit(qip_hip_state* s, uint32_t turn, size_t bytes) {
+  HIPCHK(hipMemcpyAsync(s->d_diag, s->h_diag[turn], bytes, hipMemcpyHostToDevice, s->stream));
+  HIPCHK(hipEventRecord(s->diag_uploaded[turn], s->stream));
+  return QIP_OK;
+}
+
+static int diag_upload(qip_hip_state* s, const DiagPlan& plan, const DiagGeom& g, DiagSumDesc* d) {
+  const size_t nterms = plan.terms.size(), ngroups = plan.group_mask.size();
+  const size_t off_start = nterms * sizeof(DiagTerm), off_mask = off_start + (ngroups + 1) * sizeof(uint32_t);
+  const size_t bytes = off_mask + ngroups * sizeof(uint32_t);
+  char* h = nullptr;
+  uint32_t turn = 0;
+  QCHK(table_stage(s, bytes, &h, &turn));
   memcpy(h, plan.terms.data(), nterms * sizeof(DiagTerm));
   memcpy(h + off_start, plan.group_start.data(), (ngroups + 1) * sizeof(uint32_t));
   memcpy(h + off_mask, plan.group_mask.data(), ngroups * sizeof(uint32_t));
-  HIPCHK(hipMemcpyAsync(s->d_diag, h, bytes, hipMemcpyHostToDevice, s->stream));
-  HIPCHK(hipEventRecord(s->diag_uploaded[turn], s->stream));
+  QCHK(table_commit(s, turn, bytes));
   d->terms = (const DiagTerm*)s->d_diag;
   d->group_start = (const uint32_t*)((const char*)s->d_diag + off_start);
   d->group_mask = (const uint32_t*)((const char*)s->d_diag + off_mask);
