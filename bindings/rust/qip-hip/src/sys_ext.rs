@@ -2,9 +2,20 @@
 //! `QIPX_ABI_VERSION`).  `sys.rs` stays the binding contract of `include/qip_hip.h`; `tests/test_hipx_contract_cpu.py` compares
 //! this file with the header.
 use crate::sys::qip_hip_state;
-use std::os::raw::{c_double, c_int};
+use std::os::raw::{c_char, c_double, c_int};
 
 pub const QIPX_ABI_VERSION: c_int = 1;
+
+/// `struct qipx_channel`: `count` Kraus operators of 2 * 4^k doubles each (row-major, bit i of a row = qubit `indices[i]`) on
+/// the `k` qubits `indices`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct qipx_channel {
+    pub indices: *const u64,
+    pub k: u32,
+    pub kraus: *const c_double,
+    pub count: u32,
+}
 
 extern "C" {
     pub fn qipx_abi_version() -> c_int;
@@ -157,5 +168,44 @@ extern "C" {
         k: u32,
         mode: c_int,
         passes: *mut u32,
+    ) -> c_int;
+    /// psi <- (the 2^k x 2^k `matrix` on `indices`) psi in place, unitary or not, and `rho_next` = the raw reduced density matrix
+    /// of the RESULT on `next_indices` from the same pass (conventions of `qipx_state_reduced_density`).  k, k2 in {1, 2}; the
+    /// lists may overlap; together at most three qubits.  Complete on return.
+    pub fn qipx_state_apply_reduce(
+        s: *mut qip_hip_state,
+        indices: *const u64,
+        k: u32,
+        matrix: *const c_double,
+        next_indices: *const u64,
+        k2: u32,
+        rho_next: *mut c_double,
+    ) -> c_int;
+    /// One trajectory step through `nch` channels in order: branch i of channel c is drawn by `rand_u01[c]` with weight
+    /// Re Tr(K_i^H K_i rho) and psi <- K_i psi, rescaled to the norm it had.  `chosen[c]` = i; `weights` (nullable) gets every
+    /// channel's weights one after another.
+    pub fn qipx_state_apply_channels(
+        s: *mut qip_hip_state,
+        ch: *const qipx_channel,
+        nch: u64,
+        rand_u01: *const c_double,
+        chosen: *mut u32,
+        weights: *mut c_double,
+    ) -> c_int;
+    /// The passes over the vector that `qipx_state_apply_channels` makes for the list on `n` qubits and how many of them are
+    /// fused apply-and-reduce passes (for a Complex<f64> state), after the same checks of the list.  Host-only.
+    pub fn qipx_channel_passes(n: u32, ch: *const qipx_channel, nch: u64, passes: *mut u64, fused: *mut u64) -> c_int;
+    /// The same for the state `s` (its n and precision): the plan `qipx_state_apply_channels` runs on it.  Host-only.
+    pub fn qipx_state_channel_passes(s: *mut qip_hip_state, ch: *const qipx_channel, nch: u64, passes: *mut u64, fused: *mut u64) -> c_int;
+    /// The kernel classes of the profile: those of `qip_hip_kernel_class_count` under their indices, then the classes of the
+    /// calls of this header.
+    pub fn qipx_kernel_class_count() -> c_int;
+    pub fn qipx_kernel_class_name(cls: c_int) -> *const c_char;
+    pub fn qipx_state_profile_get(
+        s: *mut qip_hip_state,
+        cls: c_int,
+        launches: *mut u64,
+        total_ms: *mut c_double,
+        algorithmic_bytes: *mut c_double,
     ) -> c_int;
 }

@@ -479,6 +479,100 @@ int qipx_state_apply_function(qip_hip_state* s, const uint64_t* in_qubits, uint3
 int qipx_function_passes(uint32_t n, const uint64_t* in_qubits, uint32_t m, const uint64_t* out_qubits, uint32_t k, int mode,
                          uint32_t* passes);
 
+/* Noise channels on a device state by quantum trajectories.  (Purely additive again.)
+ *
+ * A channel {K_i} on one or two qubits acts on a state vector by drawing branch i with probability |K_i psi|^2 / |psi|^2 and
+ * replacing psi by K_i psi, rescaled to the old norm.  Every branch weight comes from ONE read, |K_i psi|^2 = Tr(K_i^H K_i rho)
+ * with rho the reduced density matrix on the channel's qubits, and the pass that applies the chosen operator of one channel forms
+ * rho for the NEXT channel from the amplitudes it holds anyway: a chain of nch channels costs nch + 1 passes over the vector, not
+ * 2 nch.
+ *
+ * qipx_state_apply_reduce is that pass by itself: psi <- (A on `indices`) psi in place, A any complex 2^k x 2^k matrix (2 * 4^k
+ * doubles, row-major, bit i of a row = qubit indices[i], the convention of qipx_state_reduced_density), unitary or not; rho_next
+ * = the raw reduced density matrix of the RESULT on next_indices, layout and conventions of qipx_state_reduced_density.
+ * Supported: k, k2 in {1, 2}; the lists may overlap or be equal; together they cover at most three qubits.  More (k or k2 = 3,
+ * a union of four) is QIP_ERR_UNSUPPORTED; the message of a union of four names both lists.  k or k2 = 0, an index >= n, a repeated
+ * index within a list, a null pointer and a null handle are QIP_ERR_INVALID; an unusable handle is QIP_ERR_DEVICE.  Everything is
+ * checked before the first launch: on a refusal neither the state nor rho_next is touched.
+ *
+ * Kernel.  ONE launch of k_apply_density_small (csrc/qip_channel_kernels.h) plus the fold.  G is the sorted union of the two
+ * lists' index positions; the gather is the k <= 3 density kernel's on G (high positions walked, lane-id bits transposed in the
+ * wave, the packed half bit of Complex<f32>), every element read once with a non-temporal 16-byte load and written once, in
+ * place, to the address it came from; no second buffer, no atomics, and no lane writes what another lane reads.  The host hands
+ * the operator over expanded to G (A on its qubits, the identity on the rest) as kernel arguments in double.
+ *
+ * Arithmetic.  y[a] = sum_a' W[a][a'] x[a'] in double for both precisions (f32 amplitudes widened first, the result rounded once
+ * to f32): per part one chain of fused multiply-adds in ascending a' (Re: wr xr', then -wi xi'; Im: wr xi', then wi xr').  An
+ * operator that is diagonal on G (the identity and every diagonal A) runs a kernel variant that looks at W[a][a] only and does not
+ * multiply by a real or imaginary part that is exactly zero: the identity returns every amplitude bit for bit, and a zero on the
+ * diagonal gives exactly +0.  Every other operator multiplies all 2^|G| entries of a row, the zeros of the identity padding
+ * included (a row whose products are all zero still gives exactly +0; measured, the uniform loop beats skipping entries by
+ * flags, profiles/noise.md).  rho is formed from the STORED result
+ * (the f32-rounded value for a Complex<f32> state) by the products and fused multiply-adds of qipx_state_reduced_density on G;
+ * the host then sums over the qubits of G that are not in next_indices, in ascending order of their bits, and moves rows and
+ * columns to the caller's order.  The entries a <= a' are computed once and mirrored: rho_next is exactly Hermitian with +0.0
+ * diagonal imaginary parts, and a permuted next_indices list gives the bit-exact row/column permutation.
+ *
+ * Determinism.  One partial matrix per block in the handle's reduction scratch (at most 4096 blocks of 4^|G| doubles, 2 MiB, plus
+ * one matrix), folded entry by entry in block order on the device.  The same call on the same state returns the same bits, in
+ * the state and in rho_next.
+ *
+ * Error statement.  An amplitude of the result is within (2 M + 2) u |A|_F |x| of the exact product for its group x of M = 2^|G|
+ * amplitudes (u = 2^-53; one more rounding to 2^-24 for Complex<f32>): well inside 1e-12 |A| |psi| and 1e-5 |A| |psi|.  An entry of
+ * rho_next is within c u * 2 S of the exact sum over the stored amplitudes as stated for qipx_state_reduced_density, the trace
+ * over at most two further qubits adding 3 to its chain count: c <= 1106 at n = 30, below 4500, so every entry is within
+ * 1e-12 * sqrt(rho[a][a] rho[a'][a']) (tests/test_gpu_f3_noise.py holds both to these bars).
+ *
+ * Calling contract.  A relabelled state (option "tile_relabel" = 3) is put back in the caller's order on entry.  The call is
+ * ordered after the work queued on the handle and complete when it returns.
+ *
+ * qipx_state_apply_channels is the trajectory step.  ch[c].kraus holds `count` matrices of 2 * 4^k doubles each in the convention
+ * above, 1 <= count <= 16, k in {1, 2}; count = 1 is a plain gate, any matrix, taken with certainty.  For c = 0 .. nch-1 in order,
+ * with rho the raw reduced density matrix of the CURRENT state on ch[c]'s qubits:
+ *   w_i = Re Tr(K_i^H K_i rho), E_i = K_i^H K_i formed in double on the host, the trace summed over entries in row-major order;
+ *   W = sum_i w_i in index order, N = tr rho;
+ *   chosen[c] = the smallest i with rand_u01[c] * W < w_0 + .. + w_i, or the last i with w_i > 0 if none qualifies (the rule of
+ *   soft_measure: a branch of weight zero is never taken);
+ *   psi <- sqrt(N / w_chosen) K_chosen psi, the scale folded into the matrix handed to the kernel: the norm is carried through.
+ * Nothing requires sum_i K_i^H K_i = 1.  W <= 0 or a weight that is not finite is QIP_ERR_INVALID and the state is left as the
+ * preceding channels left it.  chosen[c], and weights (if not null: the w_i of all channels one after another, sum of ch[c].count
+ * doubles), are filled for every channel that ran.  rand_u01[c] must lie in [0, 1].
+ *
+ * Pass plan: one read-only reduced-density pass for ch[0]; for every c < nch-1 one fused pass (apply ch[c], reduce on ch[c+1])
+ * when the two cover at most three qubits AND the fused pass was measured faster than the two calls it replaces, otherwise a
+ * dense apply followed by a reduced-density pass; the last channel is a dense apply through the path of qip_hip_state_apply_op
+ * (in the state's precision).  Measured slower and therefore run composed (tools/bench_noise.py, profiles/noise.md): a step of
+ * three qubits on a Complex<f32> state, and for n >= 28 a step of at most two qubits none of which is an index bit inside a wave
+ * row of 64 elements (index bits 0..5; 0..6 for Complex<f32>).  nch channels on steps that fuse cost nch + 1 passes.
+ * qipx_state_channel_passes returns the plan of that handle (its n and precision) from pure host code after the same checks of
+ * the list: *passes is the number of passes over the vector, *fused how many of them are fused passes.  qipx_channel_passes is
+ * the same for a Complex<f64> state of n qubits and needs no handle and no device.
+ * Refusals before anything runs: a null handle, a null channel, index, operator, sample or result array, k = 0, an index >= n
+ * or repeated, count = 0 or > 16, a sample outside [0, 1] (QIP_ERR_INVALID); k > 2 (QIP_ERR_UNSUPPORTED).  nch = 0 does nothing.
+ * The call is complete when it returns.
+ *
+ * Profile.  The fused pass and the reduced-density call are kernel classes of the profile (option "profile"), numbered after
+ * those of qip_hip_kernel_class_count, which keep their count and indices: qipx_kernel_class_count / qipx_kernel_class_name
+ * cover both ranges and qipx_state_profile_get reads any of them, as qip_hip_state_profile_get reads the first range.
+ *
+ * Out of scope: batching many trajectories in one state, channels on three or more qubits, channels inside tile sweeps, the
+ * sharded state. */
+typedef struct qipx_channel {
+  const uint64_t* indices; /* k qubits */
+  uint32_t k;
+  const double* kraus;     /* count matrices of 2 * 4^k doubles */
+  uint32_t count;
+} qipx_channel;
+int qipx_state_apply_reduce(qip_hip_state* s, const uint64_t* indices, uint32_t k, const double* matrix, const uint64_t* next_indices,
+                            uint32_t k2, double* rho_next);
+int qipx_state_apply_channels(qip_hip_state* s, const qipx_channel* ch, uint64_t nch, const double* rand_u01, uint32_t* chosen,
+                              double* weights /* may be null */);
+int qipx_channel_passes(uint32_t n, const qipx_channel* ch, uint64_t nch, uint64_t* passes, uint64_t* fused);
+int qipx_state_channel_passes(qip_hip_state* s, const qipx_channel* ch, uint64_t nch, uint64_t* passes, uint64_t* fused);
+int qipx_kernel_class_count(void);
+const char* qipx_kernel_class_name(int cls);
+int qipx_state_profile_get(qip_hip_state* s, int cls, uint64_t* launches, double* total_ms, double* algorithmic_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,11 @@ DEBUG_SIGNATURES = {
     "qip_hip_dist_debug_pieces": (_i64, [_int, _int, _u64, _u64, _u64, C.POINTER(C.c_int32), _u64p, _u64p]),
 }
 
+class QipxChannel(C.Structure):
+    """struct qipx_channel (include/qip_hipx.h)"""
+    _fields_ = [("indices", _u64p), ("k", C.c_uint32), ("kraus", _dblp), ("count", C.c_uint32)]
+
+
 # capabilities beyond the reference's interface (include/qip_hipx.h, node QIP_HIPX: versioned on its own, not part of the
 # binding contract above)
 EXT_SIGNATURES = {
@@ -179,6 +184,13 @@ EXT_SIGNATURES = {
     "qipx_state_expect_diagonal": (_int, [_statep, _u64p, _u64p, C.POINTER(C.c_uint8), _dblp, _u64, _dblp]),
     "qipx_state_apply_function": (_int, [_statep, _u64p, _u32, _u64p, _u32, _int, _u64p, _dblp]),
     "qipx_function_passes": (_int, [_u32, _u64p, _u32, _u64p, _u32, _int, C.POINTER(C.c_uint32)]),
+    "qipx_state_apply_reduce": (_int, [_statep, _u64p, _u32, _dblp, _u64p, _u32, _dblp]),
+    "qipx_state_apply_channels": (_int, [_statep, C.POINTER(QipxChannel), _u64, _dblp, C.POINTER(C.c_uint32), _dblp]),
+    "qipx_channel_passes": (_int, [_u32, C.POINTER(QipxChannel), _u64, _u64p, _u64p]),
+    "qipx_state_channel_passes": (_int, [_statep, C.POINTER(QipxChannel), _u64, _u64p, _u64p]),
+    "qipx_kernel_class_count": (_int, []),
+    "qipx_kernel_class_name": (_cp, [_int]),
+    "qipx_state_profile_get": (_int, [_statep, _int, _u64p, _dblp, _dblp]),
 }
 
 

@@ -8,6 +8,7 @@
 // There is NO CPU fallback: without a HIP device every compute entry point fails with
 // QIP_ERR_NO_DEVICE.
 #include "qip_tile.h"
+#include "../../include/qip_hipx.h"  // (the profile's classes beyond the binding contract's)
 
 thread_local std::string g_last_error;
 
@@ -636,20 +637,33 @@ static int prof_drain(qip_hip_state* s) {
   return QIP_OK;
 }
 
-extern "C" int qip_hip_state_profile_get(qip_hip_state* s, int cls, uint64_t* launches,
-                                         double* total_ms, double* algorithmic_bytes) try {
+// one class of the profile; `count`: how many classes the caller's interface knows
+static int profile_get(qip_hip_state* s, int cls, int count, uint64_t* launches, double* total_ms, double* algorithmic_bytes) {
   STATE_ENTER_RAW(s);  // (no amplitude is addressed: a relabelled state stays as it is)
-  if (cls < 0 || cls >= KC_COUNT) return fail(QIP_ERR_INVALID, "bad kernel class %d", cls);
+  if (cls < 0 || cls >= count) return fail(QIP_ERR_INVALID, "bad kernel class %d", cls);
   QCHK(prof_drain(s));
   if (launches) *launches = s->prof_launches[cls];
   if (total_ms) *total_ms = s->prof_ms[cls];
   if (algorithmic_bytes) *algorithmic_bytes = s->prof_bytes[cls];
   return QIP_OK;
+}
+extern "C" int qip_hip_state_profile_get(qip_hip_state* s, int cls, uint64_t* launches,
+                                         double* total_ms, double* algorithmic_bytes) try {
+  return profile_get(s, cls, KC_COUNT, launches, total_ms, algorithmic_bytes);
+} QIP_CATCH_ALL
+// the classes of include/qip_hipx.h: the binding contract's first, under their indices, then KernelClassX
+static const char* kKernelClassNamesX[KCX_COUNT - KC_COUNT] = {"k_apply_density_small", "reduced_density"};
+extern "C" int qipx_kernel_class_count(void) { return KCX_COUNT; }
+extern "C" const char* qipx_kernel_class_name(int cls) {
+  return cls >= KC_COUNT && cls < KCX_COUNT ? kKernelClassNamesX[cls - KC_COUNT] : qip_hip_kernel_class_name(cls);
+}
+extern "C" int qipx_state_profile_get(qip_hip_state* s, int cls, uint64_t* launches, double* total_ms, double* algorithmic_bytes) try {
+  return profile_get(s, cls, KCX_COUNT, launches, total_ms, algorithmic_bytes);
 } QIP_CATCH_ALL
 extern "C" int qip_hip_state_profile_reset(qip_hip_state* s) try {
   STATE_ENTER_RAW(s);  // (no amplitude is addressed: a relabelled state stays as it is)
   QCHK(prof_drain(s));
-  for (int c = 0; c < KC_COUNT; ++c) {
+  for (int c = 0; c < KCX_COUNT; ++c) {
     s->prof_launches[c] = 0;
     s->prof_ms[c] = 0;
     s->prof_bytes[c] = 0;

@@ -13,6 +13,8 @@
 //                     diagonal Pauli sums in one pass, over qip_diag_plan.h (plain C++) and qip_diag_kernels.h
 //   qip_function.hip  classical functions between qubit registers (qipx_state_apply_function), over qip_function_plan.h (plain
 //                     C++) and qip_function_kernels.h; its table travels through qip_pauli.hip's table buffer
+//   qip_channel.hip   noise channels by trajectories (qipx_state_apply_reduce, qipx_state_apply_channels), over qip_channel_plan.h
+//                     (plain C++) and qip_channel_kernels.h
 //   qip_dist.hip      the sharded state (planner, pack sweep, exchange)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -112,6 +114,13 @@ enum KernelClass {
   KC_TILE_PARTS,  // (r5) not a kernel: `launches` counts the PARTS of tile sweeps that were launched in slices (TileSlicing); no time, no bytes
   KC_DENSE_SMALL, // (r6) dense k = 5..10 on a state with fewer than 16 groups (k_dense_small)
   KC_COUNT
+};
+// Classes of the calls of include/qip_hipx.h that profile: numbered on after the binding contract's, which keep their count and
+// indices (qip_hip_kernel_class_count); read through qipx_kernel_class_count / _name and qipx_state_profile_get.
+enum KernelClassX {
+  KCX_APPLY_DENSITY = KC_COUNT,  // the fused pass of the channel calls (k_apply_density_small)
+  KCX_REDUCED_DENSITY,           // qipx_state_reduced_density (k_density_small / k_density_mfma)
+  KCX_COUNT
 };
 
 template <typename T> struct HostAmp { T re, im; };  // host view of one downloaded amplitude
@@ -229,9 +238,9 @@ struct qip_hip_state {
   // profiling
   std::vector<ProfRec> pending;
   std::vector<hipEvent_t> free_events;
-  uint64_t prof_launches[KC_COUNT] = {0};
-  double prof_ms[KC_COUNT] = {0};
-  double prof_bytes[KC_COUNT] = {0};
+  uint64_t prof_launches[KCX_COUNT] = {0};
+  double prof_ms[KCX_COUNT] = {0};
+  double prof_bytes[KCX_COUNT] = {0};
 };
 
 // Device memory a recorded program owns for the payloads of its ops (dense tables, matrix-core fragments, CSR / ELL rows, tile
@@ -308,6 +317,48 @@ int pair_settle(qip_hip_state* own, qip_hip_state* other);
 // written; table_commit: that copy's stream-ordered upload to s->d_diag
 int table_stage(qip_hip_state* s, size_t bytes, char** host, uint32_t* turn);
 int table_commit(qip_hip_state* s, uint32_t turn, size_t bytes);
+
+// qip_measure.hip: the gather geometry, the block fold and the unpacking of the k <= 3 density kernels (k_density_small), which the
+// fused pass of qip_channel.hip (k_apply_density_small) shares
+struct DensSmallGeom {
+  bool packed = false, b0 = false;  // 16-byte elements of two Complex<f32>; index bit 0 (the half of such an element) is a position
+  uint32_t ke = 0, kl = 0;          // positions in elements; of these, lane-id bits
+  unsigned gx = 1;                  // blocks
+  Ins ins;                          // opens the high positions
+  DensDesc d;
+};
+DensSmallGeom dens_small_geom(const qip_hip_state* s, const std::vector<uint32_t>& sorted);
+int dens_small_collect(qip_hip_state* s, unsigned gx, uint32_t M, std::vector<double>* up);
+// The kernels of that geometry are templates over (amplitude type, KE, KL, B0, element type): `launch` is called with the one
+// that `g` and the state's precision name, as launch.template run<T, KE, KL, B0, E>(s, g).
+template <typename T, int KE, bool B0, typename E, typename L>
+static inline void dens_small_dispatch_kl(qip_hip_state* s, const DensSmallGeom& g, const L& launch) {
+  switch (g.kl) {
+    case 0: launch.template run<T, KE, 0, B0, E>(s, g); break;
+    case 1: if constexpr (KE >= 1) launch.template run<T, KE, 1, B0, E>(s, g); break;
+    case 2: if constexpr (KE >= 2) launch.template run<T, KE, 2, B0, E>(s, g); break;
+    default: if constexpr (KE >= 3) launch.template run<T, KE, 3, B0, E>(s, g); break;
+  }
+}
+template <typename T, typename E, typename L>
+static inline void dens_small_dispatch_ke(qip_hip_state* s, const DensSmallGeom& g, const L& launch) {
+  switch (g.ke) {
+    case 1: dens_small_dispatch_kl<T, 1, false, E>(s, g, launch); break;
+    case 2: dens_small_dispatch_kl<T, 2, false, E>(s, g, launch); break;
+    default: dens_small_dispatch_kl<T, 3, false, E>(s, g, launch); break;
+  }
+}
+template <typename L>
+static inline void dens_small_dispatch(qip_hip_state* s, const DensSmallGeom& g, const L& launch) {
+  if (s->dtype == QIP_C64) return dens_small_dispatch_ke<double, amp_t<double>>(s, g, launch);
+  if (!g.packed) return dens_small_dispatch_ke<float, amp_t<float>>(s, g, launch);
+  if (!g.b0) return dens_small_dispatch_ke<float, f32x4>(s, g, launch);
+  switch (g.ke) {
+    case 0: dens_small_dispatch_kl<float, 0, true, f32x4>(s, g, launch); break;
+    case 1: dens_small_dispatch_kl<float, 1, true, f32x4>(s, g, launch); break;
+    default: dens_small_dispatch_kl<float, 2, true, f32x4>(s, g, launch); break;
+  }
+}
 
 #define STATE_ENTER_NOCHECK(s)                                 \
   if (!(s)) return fail(QIP_ERR_INVALID, "null state handle"); \

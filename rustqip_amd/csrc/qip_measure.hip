@@ -588,69 +588,38 @@ static DensityGeom density_geom(const qip_hip_state* s, const std::vector<uint32
   return g;
 }
 
-template <typename T, int KE, int KL, bool B0>
-static void density_small_launch(qip_hip_state* s, const DensityGeom& g, unsigned gx, const Ins& ins, const DensDesc& d) {
-  if constexpr (std::is_same<T, float>::value) {
-    if (g.packed) {
-      hipLaunchKernelGGL((k_density_small<float, KE, KL, B0, f32x4>), dim3(gx), dim3(kBlock), 0, s->stream, (const f32x4*)s->cur, ins, d, s->d_partial);
-      return;
-    }
-  }
-  if constexpr (!B0)
-    hipLaunchKernelGGL((k_density_small<T, KE, KL, false>), dim3(gx), dim3(kBlock), 0, s->stream, (const amp_t<T>*)s->cur, ins, d, s->d_partial);
-}
-
-template <typename T, int KE, bool B0>
-static void density_small_kl(qip_hip_state* s, const DensityGeom& g, uint32_t kl, unsigned gx, const Ins& ins, const DensDesc& d) {
-  switch (kl) {
-    case 0: density_small_launch<T, KE, 0, B0>(s, g, gx, ins, d); break;
-    case 1: if constexpr (KE >= 1) density_small_launch<T, KE, 1, B0>(s, g, gx, ins, d); break;
-    case 2: if constexpr (KE >= 2) density_small_launch<T, KE, 2, B0>(s, g, gx, ins, d); break;
-    default: if constexpr (KE >= 3) density_small_launch<T, KE, 3, B0>(s, g, gx, ins, d); break;
-  }
-}
-
-// `up`: the entries a <= a' of the matrix in sorted bit order, up[2 (a M + a')] and up[.. + 1] (the rest zero)
-template <typename T>
-static int density_small_t(qip_hip_state* s, const std::vector<uint32_t>& sorted, std::vector<double>* up) {
-  const DensityGeom g = density_geom<T>(s, sorted);
-  const uint32_t k = (uint32_t)sorted.size(), ke = (uint32_t)g.pe.size(), M = 1u << k;
-  DensDesc d;
-  memset(&d, 0, sizeof d);
-  uint32_t kl = 0;
+// The geometry of the k <= 3 kernels on the sorted positions (DensDesc of qip_kernels.h), the grid, and the room for one partial
+// matrix per block plus the folded one — shared with the fused pass of qip_channel.hip, which gathers the same way.
+DensSmallGeom dens_small_geom(const qip_hip_state* s, const std::vector<uint32_t>& sorted) {
+  const DensityGeom g = s->dtype == QIP_C64 ? density_geom<double>(s, sorted) : density_geom<float>(s, sorted);
+  DensSmallGeom r;
+  r.packed = g.packed;
+  r.b0 = g.b0;
+  r.ke = (uint32_t)g.pe.size();
+  r.kl = 0;
+  memset(&r.d, 0, sizeof r.d);
   std::vector<uint32_t> high;
   for (uint32_t p : g.pe) {
-    if (p < 6) d.lpos[kl++] = p;
+    if (p < 6) r.d.lpos[r.kl++] = p;
     else high.push_back(p);
   }
-  const uint32_t kh = ke - kl;
+  const uint32_t kh = r.ke - r.kl;
   for (uint32_t c = 0; c < (1u << kh); ++c)
     for (uint32_t i = 0; i < kh; ++i)
-      if ((c >> i) & 1u) d.coff[c] |= 1ull << high[i];
+      if ((c >> i) & 1u) r.d.coff[c] |= 1ull << high[i];
   const uint64_t items = 1ull << (g.ne - kh);
-  d.nrows = std::max<uint64_t>(items >> 6, 1);
-  d.nlane = (uint32_t)std::min<uint64_t>(items, 64);
-  const uint64_t rows_per_wave_round = (uint64_t)(1u << kl) * ((1u << ke) >= 4u ? 1u : 4u >> ke);
-  const unsigned gx = (unsigned)std::min<uint64_t>(std::max<uint64_t>(d.nrows / (rows_per_wave_round * (kBlock / 64)), 1), kDensitySmallBlocks);
+  r.d.nrows = std::max<uint64_t>(items >> 6, 1);
+  r.d.nlane = (uint32_t)std::min<uint64_t>(items, 64);
+  const uint64_t rows_per_wave_round = (uint64_t)(1u << r.kl) * ((1u << r.ke) >= 4u ? 1u : 4u >> r.ke);
+  r.gx = (unsigned)std::min<uint64_t>(std::max<uint64_t>(r.d.nrows / (rows_per_wave_round * (kBlock / 64)), 1), kDensitySmallBlocks);
+  r.ins = make_ins(high, 0);
+  return r;
+}
+
+// The block fold (k_sum_partials in block order on the device), the read-back of M^2 doubles and their unpacking from the
+// kernels' accumulator slots: `up` gets the entries a <= a' in sorted bit order, up[2 (a M + a')] and up[.. + 1] (the rest zero).
+int dens_small_collect(qip_hip_state* s, unsigned gx, uint32_t M, std::vector<double>* up) {
   const size_t nout = (size_t)M * M;
-  QCHK(ensure_partial(s, (size_t)gx * nout + nout));
-  const Ins ins = make_ins(high, 0);
-  if (g.b0) {
-    if constexpr (std::is_same<T, float>::value) {
-      switch (ke) {
-        case 0: density_small_kl<float, 0, true>(s, g, kl, gx, ins, d); break;
-        case 1: density_small_kl<float, 1, true>(s, g, kl, gx, ins, d); break;
-        default: density_small_kl<float, 2, true>(s, g, kl, gx, ins, d); break;
-      }
-    }
-  } else {
-    switch (ke) {
-      case 1: density_small_kl<T, 1, false>(s, g, kl, gx, ins, d); break;
-      case 2: density_small_kl<T, 2, false>(s, g, kl, gx, ins, d); break;
-      default: density_small_kl<T, 3, false>(s, g, kl, gx, ins, d); break;
-    }
-  }
-  HIPCHK(hipGetLastError());
   const double* res = s->d_partial;
   if (gx > 1) {
     hipLaunchKernelGGL((k_sum_partials<64>), dim3(grid_for(nout, kBlock / 64)), dim3(kBlock), 0, s->stream, s->d_partial, (uint32_t)gx,
@@ -671,6 +640,24 @@ static int density_small_t(qip_hip_state* s, const std::vector<uint32_t>& sorted
     }
   }
   return QIP_OK;
+}
+
+struct DensityLaunch {  // what dens_small_dispatch launches for one (KE, KL, B0): k_density_small
+  template <typename T, int KE, int KL, bool B0, typename E>
+  void run(qip_hip_state* s, const DensSmallGeom& g) const {
+    hipLaunchKernelGGL((k_density_small<T, KE, KL, B0, E>), dim3(g.gx), dim3(kBlock), 0, s->stream, (const E*)s->cur, g.ins, g.d, s->d_partial);
+  }
+};
+
+// `up`: the entries a <= a' of the matrix in sorted bit order, up[2 (a M + a')] and up[.. + 1] (the rest zero)
+static int density_small(qip_hip_state* s, const std::vector<uint32_t>& sorted, std::vector<double>* up) {
+  const DensSmallGeom g = dens_small_geom(s, sorted);
+  const uint32_t M = 1u << sorted.size();
+  const size_t nout = (size_t)M * M;
+  QCHK(ensure_partial(s, (size_t)g.gx * nout + nout));
+  dens_small_dispatch(s, g, DensityLaunch{});
+  HIPCHK(hipGetLastError());
+  return dens_small_collect(s, g.gx, M, up);
 }
 
 template <typename T, int K>
@@ -789,8 +776,12 @@ extern "C" int qipx_state_reduced_density(qip_hip_state* s, const uint64_t* indi
   std::vector<uint32_t> sorted(k);
   for (uint32_t j = 0; j < k; ++j) sorted[j] = pos[perm[j]];
   std::vector<double> up;
-  if (k <= 3) QCHK(s->dtype == QIP_C64 ? density_small_t<double>(s, sorted, &up) : density_small_t<float>(s, sorted, &up));
-  else QCHK(s->dtype == QIP_C64 ? density_mfma_t<double>(s, sorted, &up) : density_mfma_t<float>(s, sorted, &up));
+  ProfRec rec;  // (the events bracket the launch, the fold and the read-back: one pass of the profile's class "reduced_density")
+  if (s->profile) QCHK(prof_begin(s, KCX_REDUCED_DENSITY, (double)s->amp_bytes * (double)s->namps, &rec));
+  const int rc = k <= 3 ? density_small(s, sorted, &up)
+                        : (s->dtype == QIP_C64 ? density_mfma_t<double>(s, sorted, &up) : density_mfma_t<float>(s, sorted, &up));
+  if (s->profile) QCHK(prof_end(s, &rec));  // (the pair is closed whether the pass succeeded or not)
+  QCHK(rc);
   const uint32_t M = 1u << k;
   std::vector<uint32_t> to_caller(M);
   for (uint32_t a = 0; a < M; ++a) {
@@ -816,7 +807,7 @@ extern "C" int qipx_state_reduced_density(qip_hip_state* s, const uint64_t* indi
 
 // ---- two-state reduced matrices (include/qip_hipx.h) ----------------------------------------------------------------------
 //   meet    the two handles as pauli_matrix_elements meets its own (pair_meet, pair_settle), every refusal before anything is queued
-//   launch  k_transition_small on the sorted positions, the geometry of density_small_t; one partial matrix of 2 * 4^k doubles per
+//   launch  k_transition_small on the sorted positions, the geometry of dens_small_geom; one partial matrix of 2 * 4^k doubles per
 //           block in ket's d_partial
 //   fold    k_sum_partials in block order on the device; the host moves the sorted entries to the caller's bit order
 template <typename T, int KE, int KL, bool B0>

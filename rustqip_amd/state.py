@@ -255,6 +255,43 @@ def function_passes(n: int, in_qubits, out_qubits, mode: str = "xor") -> int:
     return int(out.value)
 
 
+def _channel_args(channels):
+    """(qipx_channel array, count, what keeps its pointers alive, operators per channel) from (qubits, kraus) pairs or objects with
+    those attributes; kraus: `count` matrices of 2^k x 2^k, bit i of a row = qubit qubits[i]"""
+    channels = list(channels)
+    arr = (_ffi.QipxChannel * max(len(channels), 1))()
+    keep, counts = [], []
+    for c, ch in enumerate(channels):
+        qubits, kraus = (ch.qubits, ch.kraus) if hasattr(ch, "kraus") else ch
+        idx = np.ascontiguousarray(np.asarray([int(q) for q in qubits], dtype=np.uint64).reshape(-1))
+        k = len(idx)
+        ks = np.ascontiguousarray(np.asarray(kraus, dtype=np.complex128))
+        if k == 0 or ks.size == 0:
+            ks = ks.reshape(0, 1, 1)
+        elif ks.ndim == 2:
+            ks = ks[None]
+        if k and ks.size and (ks.ndim != 3 or ks.shape[1:] != (1 << min(k, 6), 1 << min(k, 6))):
+            raise CircuitError(f"channel {c}: operators of shape {ks.shape[1:]} on {k} qubits")
+        ks = np.ascontiguousarray(ks)
+        keep.append((idx, ks))
+        arr[c].indices = idx.ctypes.data_as(C.POINTER(C.c_uint64))
+        arr[c].k = k
+        arr[c].kraus = ks.view(np.float64).ctypes.data_as(C.POINTER(C.c_double)) if ks.size else None
+        arr[c].count = ks.shape[0]
+        counts.append(int(ks.shape[0]))
+    return arr, len(channels), keep, counts
+
+
+def channel_passes(n: int, channels) -> Tuple[int, int]:
+    """(passes over the vector, how many of them are fused apply-and-reduce passes) that HipState.apply_channels makes for
+    `channels` on an n-qubit Complex<f64> state (include/qip_hipx.h: qipx_channel_passes; host only, the call's own checks of
+    the list).  HipState.channel_passes is the plan of that state: some steps that fuse in Complex<f64> run composed in Complex<f32>."""
+    arr, nch, _keep, _ = _channel_args(channels)
+    passes, fused = C.c_uint64(), C.c_uint64()
+    _check(_ffi.lib.qipx_channel_passes(int(n), arr, nch, C.byref(passes), C.byref(fused)))
+    return int(passes.value), int(fused.value)
+
+
 def pauli_rotation_passes(n: int, terms, group: int = 0) -> int:
     """Passes over the vector HipState.apply_pauli_rotations makes for `terms` on an n-qubit state when at most `group`
     consecutive terms of one X/Y mask share a pass (0: the default of option "rotate_group").  Host only: no device is needed."""
@@ -675,6 +712,47 @@ class HipState:
         _check(_ffi.lib.qipx_state_reduced_density(self._h, _u64_array(indices), k, out.view(np.float64).ctypes.data_as(C.POINTER(C.c_double))))
         return out
 
+    def apply_reduce(self, indices: Sequence[int], matrix, next_indices: Sequence[int]) -> np.ndarray:
+        """psi <- (A on `indices`) psi in place, A any complex 2^k x 2^k matrix (bit i of a row = qubit indices[i], unitary or
+        not), and complex128[2^k2, 2^k2]: the raw reduced density matrix of the RESULT on `next_indices`, from the same pass
+        over the vector (include/qip_hipx.h: qipx_state_apply_reduce).  k, k2 in {1, 2}; the lists may overlap; together at most
+        three qubits.  Complete when it returns."""
+        indices, next_indices = [int(q) for q in indices], [int(q) for q in next_indices]
+        k, k2 = len(indices), len(next_indices)
+        m = np.ascontiguousarray(np.asarray(matrix, dtype=np.complex128))
+        if m.shape != (1 << min(k, 6), 1 << min(k, 6)):
+            raise CircuitError(f"apply_reduce: a matrix of shape {m.shape} on {k} qubits")
+        out = np.zeros((1 << min(k2, 6), 1 << min(k2, 6)), dtype=np.complex128)
+        dblp = C.POINTER(C.c_double)
+        _check(_ffi.lib.qipx_state_apply_reduce(self._h, _u64_array(indices), k, m.view(np.float64).ctypes.data_as(dblp),
+                                                _u64_array(next_indices), k2, out.view(np.float64).ctypes.data_as(dblp)))
+        return out
+
+    def apply_channels(self, channels, rand_u01) -> Tuple[np.ndarray, List[np.ndarray]]:
+        """One trajectory step through a chain of channels (include/qip_hipx.h: qipx_state_apply_channels).  `channels`:
+        (qubits, kraus) pairs or rustqip_amd.noise.Channel objects, one or two qubits each, 1 to 16 operators (one operator: a
+        plain gate); `rand_u01`: one uniform sample in [0, 1] per channel.  For each channel in order branch i is drawn with
+        probability |K_i psi|^2 / sum_j |K_j psi|^2 and psi <- K_i psi, rescaled to the norm it had.  Returns (chosen, weights):
+        uint32[len(channels)] and, per channel, float64[count] = the raw branch weights |K_i psi|^2.  nch channels cost nch + 1
+        passes over the vector where every step fuses (channel_passes says how many this state makes)."""
+        arr, nch, _keep, counts = _channel_args(channels)
+        r = np.ascontiguousarray(np.asarray(rand_u01, dtype=np.float64).reshape(-1))
+        if len(r) != nch:
+            raise CircuitError(f"apply_channels: {nch} channels but {len(r)} samples")
+        chosen = np.zeros(max(nch, 1), dtype=np.uint32)
+        weights = np.zeros(max(sum(counts), 1), dtype=np.float64)
+        _check(_ffi.lib.qipx_state_apply_channels(self._h, arr, nch, r.ctypes.data_as(C.POINTER(C.c_double)),
+                                                  chosen.ctypes.data_as(C.POINTER(C.c_uint32)), weights.ctypes.data_as(C.POINTER(C.c_double))))
+        ends = np.cumsum([0] + counts)
+        return chosen[:nch], [weights[ends[c]:ends[c + 1]].copy() for c in range(nch)]
+
+    def channel_passes(self, channels) -> Tuple[int, int]:
+        """(passes over the vector, how many of them are fused passes) that apply_channels makes for `channels` on this state"""
+        arr, nch, _keep, _ = _channel_args(channels)
+        passes, fused = C.c_uint64(), C.c_uint64()
+        _check(_ffi.lib.qipx_state_channel_passes(self._h, arr, nch, C.byref(passes), C.byref(fused)))
+        return int(passes.value), int(fused.value)
+
     def purity(self, indices: Sequence[int]) -> float:
         """tr rho^2 / (tr rho)^2 of the reduced density matrix of `indices`: 1 for a product state, 2^-k when maximally mixed"""
         rho = self.reduced_density_matrix(indices)
@@ -980,13 +1058,14 @@ class HipState:
     # -- profiling -----------------------------------------------------------------------
     def profile(self) -> dict:
         """Per-kernel-class {launches, total_ms, algorithmic_bytes} gathered while option
-        'profile' = 1 (HIP events on the handle's stream)."""
+        'profile' = 1 (HIP events on the handle's stream): the classes of include/qip_hip.h, then those of
+        include/qip_hipx.h ("k_apply_density_small": the fused pass of apply_reduce / apply_channels; "reduced_density")."""
         out = {}
-        for cls in range(_ffi.lib.qip_hip_kernel_class_count()):
+        for cls in range(_ffi.lib.qipx_kernel_class_count()):
             launches, ms, by = C.c_uint64(), C.c_double(), C.c_double()
-            _check(_ffi.lib.qip_hip_state_profile_get(self._h, cls, C.byref(launches), C.byref(ms), C.byref(by)))
+            _check(_ffi.lib.qipx_state_profile_get(self._h, cls, C.byref(launches), C.byref(ms), C.byref(by)))
             if launches.value:
-                out[_ffi.lib.qip_hip_kernel_class_name(cls).decode()] = {
+                out[_ffi.lib.qipx_kernel_class_name(cls).decode()] = {
                     "launches": int(launches.value), "total_ms": ms.value, "algorithmic_bytes": by.value,
                 }
         return out
