@@ -208,8 +208,28 @@ int qip_hip_state_create(uint32_t n, int dtype, int device, qip_hip_state** out)
  * amplitudes, `scratch` (may be NULL) a second buffer of the same size,
  * `stream` is the caller's hipStream_t, used as is (NULL = the HIP null / legacy
  * default stream, which is torch's default stream on ROCm), so kernels are ordered
- * with the caller's other work such as RCCL collectives.  The handle never frees
- * wrapped memory and never creates a stream of its own. */
+ * with the caller's other work such as RCCL collectives: every kernel, table upload
+ * and memset of the handle is issued on that stream.  The handle never frees
+ * wrapped memory and never creates a stream of its own.
+ *   Alignment: the kernels read both buffers as 16-byte elements (a Complex<f64>
+ * amplitude; TWO Complex<f32> amplitudes), so `amps` and a non-NULL `scratch` must be
+ * 16-byte aligned.  A pointer that is not (a Complex<f32> view that starts at an odd
+ * element) is refused with QIP_ERR_INVALID and a message naming it, before a device is
+ * touched.
+ *   Where the state lives: the two buffers change roles whenever a call writes out of
+ * place.  Those calls are qip_hip_state_permute_bits and _swap_buffers; apply_op /
+ * apply_ops / a program run with an op whose kernel is out of place (the literal gather
+ * of "force_generic" and of sparse ops it serves, the small-state dense kernel, dense ops
+ * too wide for registers that do not run on matrix cores, a tile sweep that ends in a
+ * bit permutation or a fold); and EVERY call that needs the caller's order of a state
+ * left relabelled by "tile_relabel" = 3, which restores it with one such sweep first.
+ * qip_hip_state_device_ptr always names the buffer that holds the state, the one
+ * _download reads; with a `scratch` given it is `amps` or `scratch`, and
+ * _scratch_ptr is the other one.  With `scratch` = NULL the library allocates the second
+ * buffer when it first needs one, so the state can end in LIBRARY memory: compare
+ * _device_ptr with `amps`, and copy the state out before _destroy.  _destroy frees
+ * exactly the buffers the library allocated, whichever role they ended in, and never
+ * `amps`, `scratch` or the stream. */
 int qip_hip_state_wrap(uint32_t n, int dtype, int device, void* amps, void* scratch,
                        void* stream, qip_hip_state** out);
 int qip_hip_state_destroy(qip_hip_state* s);
@@ -219,8 +239,9 @@ int qip_hip_state_init_basis(qip_hip_state* s, uint64_t index);
 /* Copy amplitudes [offset, offset+len) from / to host memory. */
 int qip_hip_state_upload(qip_hip_state* s, const void* src, uint64_t offset, uint64_t len);
 int qip_hip_state_download(qip_hip_state* s, void* dst, uint64_t offset, uint64_t len);
-/* Device pointer of the current amplitude buffer (may change after apply_op
- * when the out-of-place path swapped buffers). */
+/* Device pointer of the buffer that holds the state now: the one _download reads.  It changes whenever a call wrote out
+ * of place and the two buffers changed roles (the list at qip_hip_state_wrap); a relabelled state is put back in the
+ * caller's order before the address is handed out.  Valid until the next call on the handle that can exchange the buffers. */
 int qip_hip_state_device_ptr(qip_hip_state* s, void** amps);
 /* Device pointer of the second (scratch / arena) buffer, allocating it if needed, and the
  * exchange of the two buffers.  Together they let an external out-of-place step — the RCCL

@@ -437,6 +437,9 @@ extern "C" int qip_hip_state_create(uint32_t n, int dtype, int device, qip_hip_s
 extern "C" int qip_hip_state_wrap(uint32_t n, int dtype, int device, void* amps, void* scratch,
                                   void* stream, qip_hip_state** out) try {
   if (!amps) return fail(QIP_ERR_INVALID, "null amplitude buffer");
+  // the kernels read both buffers as 16-byte elements: amp_t<double>, and two Complex<f32> amplitudes as one f32x4
+  if ((uintptr_t)amps % 16) return fail(QIP_ERR_INVALID, "the amplitude buffer %p is not 16-byte aligned", amps);
+  if ((uintptr_t)scratch % 16) return fail(QIP_ERR_INVALID, "the scratch buffer %p is not 16-byte aligned", scratch);
   QCHK(state_new(n, dtype, device, out));
   qip_hip_state* s = *out;
   s->cur = amps;

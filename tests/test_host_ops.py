@@ -190,6 +190,21 @@ def test_no_gpu_fails_loudly():
         q.apply_op(1, q.MatrixOp.new_matrix([0], [0, 1, 1, 0]), np.ones(2, dtype=np.int16), np.zeros(2, dtype=np.int16))
 
 
+def test_wrap_refuses_misaligned_buffers_before_touching_a_device():
+    """qip_hip_state_wrap: the kernels read both buffers as 16-byte elements, so an amplitude or scratch pointer that is not
+    16-byte aligned (a Complex<f32> view that starts at an odd element: address 16 k + 8) is QIP_ERR_INVALID, decided with the
+    null check — before a device is looked for, so it is the answer on a box without a GPU too"""
+    for dtype in (np.complex64, np.complex128):
+        for bad in (4096 + 8, 4096 + 4, 4096 + 15):
+            with pytest.raises(q.CircuitError, match="amplitude buffer .* not 16-byte aligned"):
+                q.HipState(3, dtype, wrap_ptr=bad)
+            with pytest.raises(q.CircuitError, match="scratch buffer .* not 16-byte aligned"):
+                q.HipState(3, dtype, wrap_ptr=4096, scratch_ptr=8192 + (bad - 4096))
+    if q.device_count() == 0:  # aligned pointers pass the check and reach the device lookup
+        with pytest.raises(q.QipHipError, match="no CPU fallback"):
+            q.HipState(3, np.complex64, wrap_ptr=4096, scratch_ptr=8192)
+
+
 def test_product_never_imports_oracle():
     pkg = os.path.join(ROOT, "rustqip_amd")
     for dirpath, _, files in os.walk(pkg):
