@@ -169,6 +169,28 @@ extern "C" {
         mode: c_int,
         passes: *mut u32,
     ) -> c_int;
+    /// |x>|t> -> |x> (U_x |t>) for all 2^m values x of the `select` register in one in-place pass: `matrices` holds 2^m row-major
+    /// 2^k x 2^k complex matrices (re, im interleaved), bit i of x = qubit select[i], bit i of a row or column = qubit targets[i].
+    /// k in {1, 2}, m + 2k <= 20.  Queued on the handle's stream, returns without waiting.
+    pub fn qipx_state_apply_multiplexed(
+        s: *mut qip_hip_state,
+        select: *const u64,
+        m: u32,
+        targets: *const u64,
+        k: u32,
+        matrices: *const c_double,
+    ) -> c_int;
+    /// The bytes of the device table `qipx_state_apply_multiplexed` uploads for a state of `dtype` on `n` qubits, after the same
+    /// checks of the registers.  Host-only.
+    pub fn qipx_multiplexed_table_bytes(
+        dtype: c_int,
+        n: u32,
+        select: *const u64,
+        m: u32,
+        targets: *const u64,
+        k: u32,
+        bytes: *mut u64,
+    ) -> c_int;
     /// psi <- (the 2^k x 2^k `matrix` on `indices`) psi in place, unitary or not, and `rho_next` = the raw reduced density matrix
     /// of the RESULT on `next_indices` from the same pass (conventions of `qipx_state_reduced_density`).  k, k2 in {1, 2}; the
     /// lists may overlap; together at most three qubits.  Complete on return.

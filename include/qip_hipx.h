@@ -479,6 +479,61 @@ int qipx_state_apply_function(qip_hip_state* s, const uint64_t* in_qubits, uint3
 int qipx_function_passes(uint32_t n, const uint64_t* in_qubits, uint32_t m, const uint64_t* out_qubits, uint32_t k, int mode,
                          uint32_t* passes);
 
+/* Multiplexed (uniformly controlled) 1- and 2-qubit gates from a table in one in-place pass: for every value x of a select register
+ * the matrix U_x on one or two target qubits,
+ *   |x>|t>  ->  |x> (U_x |t>)        for all 2^m values x in one call,
+ * the non-diagonal counterpart of the table calls above: Moettoenen state preparation and isometries, QROM-controlled rotations,
+ * the SELECT of a block encoding on small targets, a batch of parameter sets held in one state.  (Purely additive again.)
+ *
+ * Registers.  select[0..m) and targets[0..k) are disjoint lists of distinct qubits (qubit q = index bit n-1-q); bit i of x is the bit
+ * of qubit select[i]; bit i of a matrix row or column is the bit of qubit targets[i] (the convention of qipx_state_apply_reduce).
+ * `matrices` holds 2^m matrices of 2 * 4^k doubles each, row-major, re and im interleaved; entry x is U_x, any complex matrix,
+ * unitary or not.  k is 1 or 2, m + 2k <= 20 (a table of at most 16 MiB in Complex<f64>), m + k <= n; m = 0 is a plain gate.
+ *
+ * Arithmetic.  Every table entry is rounded once to the state's precision.  With M = 2^k, for each group v of the M amplitudes that
+ * share x and every other bit, in the state's precision and with no fused multiply-add,
+ *   p_a' = ( fl(fl(wr xr) - fl(wi xi)), fl(fl(wr xi) + fl(wi xr)) )      w = U_x[a][a'], x = v[a']
+ *   y_a  = p_0, then y_a = fl(y_a + p_a') for a' = 1 .. M-1 in ascending order
+ * (zero entries are multiplied like any other).  If row a of the rounded matrix is exactly the unit row e_a (1 at a, zeros of
+ * either sign elsewhere), y_a is v_a with its bits, signed zeros and non-finite values included: a controlled multiplexed gate is
+ * a table whose matrices are the identity wherever the control bit of x reads 0, and those amplitudes stay untouched, as under
+ * apply_op.  To first order |y_a - exact| <= sqrt(2) (M + 2) u |U_x[a]|_2 |v|_2, u = 2^-53 or 2^-24: a term passes one product
+ * rounding (sqrt(2) u relative, both parts) and at most M further roundings of the sum, Cauchy-Schwarz bounds the sum of the term
+ * magnitudes by |U_x[a]|_2 |v|_2, and one more u covers the rounded table.  The tests hold the arithmetic to (1.5 M + 3) u of
+ * that norm product (6 u for k = 1, 9 u for k = 2) and the kernel bit for bit to the arithmetic.
+ *
+ * Cost.  One launch, one pass: every amplitude is loaded once and stored once to the address it came from, as whole wave rows, no
+ * LDS staging, no atomics, no second buffer.  A lane holds the amplitudes of its group whose target bits lie outside the six low
+ * index bits and gets the others from its wave by shuffles; it keeps only the matrix rows it stores, and fetches them again only
+ * when a select bit of its index changes along its walk, which is ordered so that the other bits vary first.  The table lives in
+ * the device buffer of the handle that qipx_state_apply_diagonal and qipx_state_apply_function use.  Measured at n = 30
+ * (tools/bench_multiplex.py, profiles/multiplex.md), Complex<f64> / Complex<f32>: 5.8 - 6.4 / 2.9 - 3.1 ms for m <= 10 with a target
+ * among the six low index bits, wherever the select bits sit (1.07 - 1.21 / 1.06 - 1.12 dense gate passes on the same targets), 6.9 -
+ * 7.4 / 3.7 - 3.9 ms with two targets outside them; m = 16 pays for rounding and uploading its table on top (k = 2: 8.7 - 8.9 / 5.0 -
+ * 5.1 ms; at n = 26 the table is most of the call).  2^m controlled gates through apply_ops cost 2.2 - 3.2 / 4.2 - 6.4 times the call at
+ * m = 4, and one block-diagonal dense op on 6 qubits 1.30 / 1.58 times.  The call LOSES at the small end: to 4 controlled gates at
+ * m = 2, k = 1 in Complex<f64> (5.6 - 5.7 against 6.2 - 6.3 ms), and to one block-diagonal dense op on m + k = 3 .. 5 qubits in
+ * Complex<f64> (5.3 - 6.1 against 6.0 - 6.3 ms) and on 3 .. 4 qubits in Complex<f32> (2.7 - 2.9 against 2.9 - 3.1 ms): the pass runs
+ * at about 85 % of a gate pass's bandwidth, which is open.
+ *
+ * Calling contract.  That of qipx_state_apply_function: the state is changed in place, the launch is queued on the handle's stream
+ * and the call returns without waiting (a relabelled state is put back in the caller's order first; an unusable one is refused
+ * with QIP_ERR_DEVICE); `matrices` may be freed or rewritten as soon as the call returns.  Each of these is QIP_ERR_INVALID with a
+ * message, before anything is queued, the state untouched: a null handle (there is no host fall-back); a qubit >= n ("out of
+ * range"), listed twice ("repeated") or in both registers; k = 0 or k > 2; m + 2k > 20; a null qubit array of a non-empty
+ * register; a null `matrices` ("null matrix array"); an entry that is not finite.
+ *
+ * qipx_multiplexed_table_bytes is host-only: the bytes of the device table for a state of `dtype` (QIP_C64 / QIP_C32) on n qubits,
+ * after the same checks of the registers with the same messages.  It needs no device.
+ *
+ * Out of scope: three or more target qubits, multiplexed Pauli strings, recording the call into programs / hipGraph, apply_ops
+ * fusion, the sharded state, the builder, replay and QASM, the C++ mirror.  There is no option, and the launch is not a kernel
+ * class of the profile. */
+int qipx_state_apply_multiplexed(qip_hip_state* s, const uint64_t* select, uint32_t m, const uint64_t* targets, uint32_t k,
+                                 const double* matrices);
+int qipx_multiplexed_table_bytes(int dtype, uint32_t n, const uint64_t* select, uint32_t m, const uint64_t* targets, uint32_t k,
+                                 uint64_t* bytes);
+
 /* Noise channels on a device state by quantum trajectories.  (Purely additive again.)
  *
  * A channel {K_i} on one or two qubits acts on a state vector by drawing branch i with probability |K_i psi|^2 / |psi|^2 and

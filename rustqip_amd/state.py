@@ -255,6 +255,31 @@ def function_passes(n: int, in_qubits, out_qubits, mode: str = "xor") -> int:
     return int(out.value)
 
 
+def _multiplexed_args(select, targets, matrices):
+    sel = np.ascontiguousarray(np.asarray(list(select), dtype=np.uint64).reshape(-1))
+    tgt = np.ascontiguousarray(np.asarray(list(targets), dtype=np.uint64).reshape(-1))
+    m, k = len(sel), len(tgt)
+    mats = None
+    if matrices is not None:
+        mats = np.ascontiguousarray(np.asarray(matrices, dtype=np.complex128))
+        if 1 <= k <= 2 and m + 2 * k <= 20 and mats.shape != (1 << m, 1 << k, 1 << k):
+            raise CircuitError(f"apply_multiplexed: matrices of shape {mats.shape} for {m} select and {k} target qubits, "
+                               f"({1 << m}, {1 << k}, {1 << k}) is needed")
+    u64p = C.POINTER(C.c_uint64)
+    keep = (sel, tgt, mats)  # (the arrays behind the pointers)
+    return (sel.ctypes.data_as(u64p), m, tgt.ctypes.data_as(u64p), k,
+            None if mats is None else mats.ctypes.data_as(C.POINTER(C.c_double))), keep
+
+
+def multiplexed_table_bytes(n: int, select, targets, dtype=np.complex128) -> int:
+    """bytes of the device table HipState.apply_multiplexed uploads for these registers on an n-qubit state of `dtype`
+    (include/qip_hipx.h: qipx_multiplexed_table_bytes; host-only, the call's own checks of the registers)"""
+    args, _keep = _multiplexed_args(select, targets, None)
+    out = C.c_uint64(0)
+    _check(_ffi.lib.qipx_multiplexed_table_bytes(_dtype_of(np.empty(0, dtype=dtype)), int(n), *args[:4], C.byref(out)))
+    return int(out.value)
+
+
 def _channel_args(channels):
     """(qipx_channel array, count, what keeps its pointers alive, operators per channel) from (qubits, kraus) pairs or objects with
     those attributes; kraus: `count` matrices of 2^k x 2^k, bit i of a row = qubit qubits[i]"""
@@ -665,6 +690,22 @@ class HipState:
     def function_passes(self, in_qubits, out_qubits, mode: str = "xor") -> int:
         """how many passes over the vector apply_function makes for these registers and this mode (host-only)"""
         return function_passes(self.n, in_qubits, out_qubits, mode)
+
+    def apply_multiplexed(self, select, targets, matrices) -> None:
+        """|x>|t> -> |x> (U_x |t>) for every value x of the `select` register in one in-place pass (include/qip_hipx.h:
+        qipx_state_apply_multiplexed).  `matrices` is an array-like of shape (2^m, 2^k, 2^k), entry x = U_x, any complex matrices;
+        bit i of x is qubit select[i], bit i of a row or column is qubit targets[i]; k is 1 or 2 and m + 2k <= 20.  A row that is
+        exactly a unit row leaves its amplitude untouched, so identity matrices make controls.  Queued on the handle's stream:
+        returns without waiting, and `matrices` may be changed at once.
+        Measured at n = 30 (profiles/multiplex.md), Complex<f64> / Complex<f32>: one pass 5.8 - 6.4 / 2.9 - 3.1 ms for m <= 10 with a
+        target inside the wave row, whatever the select placement (1.07 - 1.21 / 1.06 - 1.12 gate passes on the same targets), up to
+        7.4 / 3.9 ms with both of two targets outside the row; m = 16 adds the staging of its table (k = 2: 8.7 - 8.9 / 5.0 - 5.1 ms, and
+        at n = 26 four to seven gate passes).  Against 16 controlled gates through apply_ops (m = 4) 2.2 - 3.2 / 4.2 - 6.4 times
+        faster, against one block-diagonal dense op on 6 qubits 1.30 / 1.58 times faster; it LOSES to 4 controlled gates at m = 2,
+        k = 1 in Complex<f64> (6.2 - 6.3 against 5.6 - 5.7 ms) and to the block-diagonal dense op on 3 - 5 qubits in Complex<f64>
+        (6.0 - 6.3 against 5.3 - 6.1 ms) and on 3 - 4 qubits in Complex<f32> (2.9 - 3.1 against 2.7 - 2.9 ms)."""
+        args, _keep = _multiplexed_args(select, targets, matrices)
+        _check(_ffi.lib.qipx_state_apply_multiplexed(self._h, *args))
 
     def _partner(self, other: "HipState", what: str) -> None:
         if not isinstance(other, HipState):
