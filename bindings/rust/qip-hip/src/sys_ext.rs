@@ -5,6 +5,9 @@ use crate::sys::qip_hip_state;
 use std::os::raw::{c_char, c_double, c_int};
 
 pub const QIPX_ABI_VERSION: c_int = 1;
+/// `flags` of `qipx_state_apply_qft`: the inverse transform; the register's bits in reversed order on the transformed side.
+pub const QIPX_QFT_INVERSE: u32 = 1;
+pub const QIPX_QFT_REVERSED: u32 = 2;
 
 /// `struct qipx_channel`: `count` Kraus operators of 2 * 4^k doubles each (row-major, bit i of a row = qubit `indices[i]`) on
 /// the `k` qubits `indices`.
@@ -190,6 +193,26 @@ extern "C" {
         targets: *const u64,
         k: u32,
         bytes: *mut u64,
+    ) -> c_int;
+    /// The quantum Fourier transform of the register `qubits` (bit i of its value = qubit qubits[i]) for every setting of the other
+    /// qubits, in place: new[y] = 2^(-m/2) sum_x exp(+-2 pi i x y / 2^m) old[x], the minus sign with `QIPX_QFT_INVERSE`;
+    /// `QIPX_QFT_REVERSED` leaves the forward result bit-reversed and reads the inverse's input in that order.  FFT passes over LDS
+    /// tiles, per fibre within 8 m u of the exact transform.  Queued on the handle's stream, returns without waiting.
+    pub fn qipx_state_apply_qft(
+        s: *mut qip_hip_state,
+        qubits: *const u64,
+        m: u32,
+        flags: u32,
+    ) -> c_int;
+    /// The passes over the vector that `qipx_state_apply_qft` makes for a state of `dtype` on `n` qubits, after the same checks.
+    /// Host-only.
+    pub fn qipx_qft_passes(
+        dtype: c_int,
+        n: u32,
+        qubits: *const u64,
+        m: u32,
+        flags: u32,
+        passes: *mut u32,
     ) -> c_int;
     /// psi <- (the 2^k x 2^k `matrix` on `indices`) psi in place, unitary or not, and `rho_next` = the raw reduced density matrix
     /// of the RESULT on `next_indices` from the same pass (conventions of `qipx_state_reduced_density`).  k, k2 in {1, 2}; the

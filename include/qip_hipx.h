@@ -534,6 +534,80 @@ int qipx_state_apply_multiplexed(qip_hip_state* s, const uint64_t* select, uint3
 int qipx_multiplexed_table_bytes(int dtype, uint32_t n, const uint64_t* select, uint32_t m, const uint64_t* targets, uint32_t k,
                                  uint64_t* bytes);
 
+/* The quantum Fourier transform of a qubit register in FFT passes: the piece that closes period finding and phase estimation
+ * after qipx_state_apply_function and qipx_state_apply_multiplexed.  (Purely additive again.)
+ *
+ * Register.  qubits[0..m) are distinct qubits (qubit q = index bit n-1-q); bit i of the register value is the bit of qubits[i]
+ * (LSB first, as in qipx_state_apply_function, measure_probs and qipx_state_reduced_density), anywhere and in any order, 0 <= m <= n.
+ *
+ * Definition.  For every fibre (the M = 2^m amplitudes that share all other index bits):
+ *   flags = 0                                 new[y] = M^(-1/2) sum_x exp(+2 pi i x y / M) old[x]
+ *   QIPX_QFT_INVERSE                          the same with exp(-2 pi i x y / M)
+ *   QIPX_QFT_REVERSED                         forward, the result left with the register's bits in reversed order: the amplitude
+ *                                             of output value y sits where the register reads rev_m(y)
+ *   QIPX_QFT_REVERSED | QIPX_QFT_INVERSE      the input is read in that reversed order and the output is natural: the call
+ *                                             after a QIPX_QFT_REVERSED call is the identity
+ * m = 0 does nothing.  Sign and order are the reference's qfft: with qubits = [n-1, .., 0] and flags = 0 the call equals the
+ * lowered circuit of m Hadamards, m(m-1)/2 controlled phases and m/2 swaps on the whole register with qubit 0 the most
+ * significant bit.
+ *
+ * Arithmetic.  Not bit-exact to anything: per fibre, with u = 2^-53 or 2^-24 by the state's precision,
+ *   |got_fibre - exact_fibre|_2 <= 8 m u |old_fibre|_2,
+ * a first-order worst case: a radix-2 stage costs one rounding for the sum or difference, two for the 1/sqrt2 scale and its rounded
+ * constant, sqrt(5) u for the product with a twiddle and 1.5 u for the twiddle itself (under 6.8 u per stage), plus one more twiddle
+ * product per pass.  Every twiddle exponent is formed exactly in integers modulo its power of two before any floating-point
+ * operation; for both precisions the sine and cosine come from double arithmetic (a per-pass table built by the host's libm from
+ * an octant-reduced exponent for the stages, a device evaluation in double for the one outer twiddle per amplitude and pass) and
+ * are rounded once to the state's precision.  The scale 2^(-L/2) of a pass of L stages is applied once, folded into the outer
+ * twiddle.  Fibres never mix: a fibre that is zero on entry is zero on exit, of either sign.  No atomics: the same call on the
+ * same state gives the same bits, whatever the grid.
+ *
+ * Cost.  Decimation in frequency from the register's most significant bit down.  A pass takes a contiguous range of register
+ * bits whose index positions fit one tile, the wave row (index positions 0..5) plus at most 6 register positions outside it,
+ * cut greedily from the top; register bits inside the row are free.  A block loads its tile as whole rows into LDS (64 KiB of
+ * Complex<f64> at most, two blocks per CU), runs up to 12 radix-2 stages on it, three at a time in registers, multiplies by the
+ * outer twiddle and stores the rows back in place: every amplitude is read once and written once per pass.  Every group of three
+ * stages exchanges through LDS, the stages on bits of the wave row included: wave shuffles for those are NOT built, so a pass of
+ * 12 stages makes four LDS round trips beside its staging.  With h register
+ * positions outside the row there are P = max(1, ceil(h / 6)) tile passes.  QIPX_QFT_REVERSED runs exactly these and never
+ * touches the scratch buffer.  Natural order in ONE pass is one pass (the digit reversal is a slot permutation on the way out of
+ * LDS); natural order with P > 1 closes with one bit-reversal sweep through the bit-permutation kernel of
+ * qip_hip_state_permute_bits, P + 1 passes: THIS case allocates the handle's scratch buffer (or uses the caller's, for a wrapped
+ * state) before anything is queued and leaves the result in it as the current buffer, as qip_hip_state_permute_bits does.  The twiddle tables (at most
+ * 32 KiB per pass) live in the device buffer of the handle that qipx_state_apply_diagonal, qipx_state_apply_function and
+ * qipx_state_apply_multiplexed use.
+ * Measured at n = 30 (tools/bench_qft.py, profiles/qft.md), Complex<f64> / Complex<f32>, beside one H gate pass of 5.3 / 2.8 ms: a tile
+ * pass of 12 stages takes 10.4 - 10.6 / 7.9 ms (2.0 / 2.8 gate passes: it is bound by its LDS round trips and arithmetic, not by
+ * memory, which is open); m = 12 on the top index bits 14.4 / 9.9 ms reversed (2 passes) and 19.7 / 12.5 ms natural (3); m = 16 on
+ * the top bits 21.4 / 14.3 and 26.7 / 16.8 ms; m = n = 30 34.5 / 24.7 ms reversed (4 passes) and 40.9 / 28.4 ms natural (5).  The
+ * lowered circuit through apply_ops was timed in three modes.  Default (the interpreter's sweeps): 1.22 - 2.35 / 1.04 - 1.89 times
+ * the call on every shape (m = n = 30 natural: 96.0 / 53.7 ms).  Compiled IEEE-equal sweeps (tile = 1 + tile_jit): the call wins on
+ * every shape in Complex<f64> (whole register 40.9 against 59.6 ms) and LOSES in Complex<f32> on m = 12 on the low bits reversed
+ * (7.86 against 7.20 ms) and on m = 16 (16.84 against 16.76 and 14.31 against 13.56 ms).  The 1e-12 mode (tile = 2 + tile_jit +
+ * tile_fma + tile_merge): in Complex<f64> the call wins on m = 12 and m = 16 (1.05 - 1.52 times) and LOSES on the whole register,
+ * 40.9 against 35.1 ms natural and 34.5 against 28.4 ms reversed; in Complex<f32> it wins only on m = 12 natural on the low bits
+ * (1.12) and m = 12 on the top bits (1.03 - 1.04) and LOSES on m = 12 low reversed (7.86 against 6.15 ms), m = 16 (16.8 against
+ * 16.2 and 14.3 against 13.2 ms) and the whole register (28.4 against 20.2 and 24.7 against 16.9 ms).  At n = 26 Complex<f64> also
+ * LOSES on m = 16 (1.70 against 1.55 ms) and is level on the whole register.
+ *
+ * Calling contract.  That of qipx_state_apply_function: the state is changed in place, the launches are queued on the handle's
+ * stream and the call returns without waiting (a relabelled state is put back in the caller's order first; an unusable one is
+ * refused with QIP_ERR_DEVICE); `qubits` may be freed or rewritten as soon as the call returns.  Each of these is QIP_ERR_INVALID
+ * with a message, before anything is queued, the state untouched: a null handle (there is no host fall-back); a null `qubits` with
+ * m > 0 ("null qubit array"); a qubit >= n ("out of range"); a qubit listed twice ("repeated"); unknown flag bits.
+ *
+ * qipx_qft_passes is host-only: the passes over the vector that the call makes on a state of `dtype` (QIP_C64 / QIP_C32) on n
+ * qubits, P with QIPX_QFT_REVERSED or when P = 1, P + 1 otherwise, 0 for m = 0, after the same checks with the same messages.  It
+ * needs no device.  (`dtype` is there so that Complex<f32> may later take seven positions per pass; both precisions take six.)
+ *
+ * Out of scope: the approximate QFT that drops small rotations, transforms of non-power-of-two size, the sharded state,
+ * recording the call into programs / hipGraph, apply_ops fusion, the builder, replay and QASM, the C++ mirror.  There is no
+ * option, and the launches are not a kernel class of the profile (the closing sweep counts as the bit permutation it is). */
+#define QIPX_QFT_INVERSE 1u
+#define QIPX_QFT_REVERSED 2u
+int qipx_state_apply_qft(qip_hip_state* s, const uint64_t* qubits, uint32_t m, uint32_t flags);
+int qipx_qft_passes(int dtype, uint32_t n, const uint64_t* qubits, uint32_t m, uint32_t flags, uint32_t* passes);
+
 /* Noise channels on a device state by quantum trajectories.  (Purely additive again.)
  *
  * A channel {K_i} on one or two qubits acts on a state vector by drawing branch i with probability |K_i psi|^2 / |psi|^2 and

@@ -9,6 +9,7 @@ Public surface (mirrors the reference names for this path):
   circuits workload generators of BASELINE.json's configs
   classical  copy, add, add_const, exp_mod_into, phase_oracle on qubit registers: thin calls of HipState.apply_function
   multiplex  rotation, select_gates, controlled, prepare_register: thin calls of HipState.apply_multiplexed
+  fourier  qft, iqft, qft_ops, phase_estimation_readout, order_finding: thin calls of HipState.apply_qft
   noise    Channel and the usual Kraus families, trajectory and average: thin calls of HipState.apply_channels
 Importing the package loads rustqip_amd/lib/libqip_hip.so and fails loudly if it is missing.
 """
@@ -19,13 +20,14 @@ from .state import (HipState, QipHipError, apply_op, apply_op_device, apply_op_o
                     make_op_matrix, set_global_option)
 from .builder import Conditioned, HipBuilder, Measurements, Register, lower_to_matrix_op
 from .state import DeviceSlice, HipProgram, expect_pauli_passes, ext_abi_version, pauli_rotation_passes, pauli_sum_passes, von_neumann_entropy
-from .state import channel_passes, function_passes, multiplexed_table_bytes, krylov_bar, tridiagonal_eigh, tridiagonal_propagator_column
+from .state import channel_passes, function_passes, multiplexed_table_bytes, qft_passes, krylov_bar, tridiagonal_eigh, tridiagonal_propagator_column
 from . import circuits  # noqa: F401  (workload generators: rustqip_amd.circuits)
 from . import parametric  # noqa: F401  (parametrised gates and the plan of HipState.circuit_gradient)
 from . import replay  # noqa: F401  (flat circuit-replay format)
 from . import classical  # noqa: F401  (classical reversible arithmetic on registers through HipState.apply_function)
 from . import multiplex  # noqa: F401  (multiplexed rotations, gate lists and state preparation through HipState.apply_multiplexed)
 from . import noise  # noqa: F401  (noise channels by quantum trajectories through HipState.apply_channels)
+from . import fourier  # noqa: F401  (the quantum Fourier transform of a register and what it closes, through HipState.apply_qft)
 
 __all__ = [
     "CircuitError", "MatrixOp", "Representation", "algorithmic_bytes", "flip_bits", "make_control_op",
@@ -34,4 +36,5 @@ __all__ = [
     "HipBuilder", "Measurements", "Register", "lower_to_matrix_op", "HipProgram", "DeviceSlice", "circuits", "replay", "ext_abi_version", "expect_pauli_passes",
     "pauli_rotation_passes", "pauli_sum_passes", "von_neumann_entropy", "krylov_bar", "tridiagonal_eigh", "tridiagonal_propagator_column",
     "inverse_op", "parametric", "classical", "function_passes", "noise", "channel_passes", "multiplex", "multiplexed_table_bytes",
+    "fourier", "qft_passes",
 ]

@@ -186,6 +186,8 @@ EXT_SIGNATURES = {
     "qipx_function_passes": (_int, [_u32, _u64p, _u32, _u64p, _u32, _int, C.POINTER(C.c_uint32)]),
     "qipx_state_apply_multiplexed": (_int, [_statep, _u64p, _u32, _u64p, _u32, _dblp]),
     "qipx_multiplexed_table_bytes": (_int, [_int, _u32, _u64p, _u32, _u64p, _u32, _u64p]),
+    "qipx_state_apply_qft": (_int, [_statep, _u64p, _u32, _u32]),
+    "qipx_qft_passes": (_int, [_int, _u32, _u64p, _u32, _u32, C.POINTER(C.c_uint32)]),
     "qipx_state_apply_reduce": (_int, [_statep, _u64p, _u32, _dblp, _u64p, _u32, _dblp]),
     "qipx_state_apply_channels": (_int, [_statep, C.POINTER(QipxChannel), _u64, _dblp, C.POINTER(C.c_uint32), _dblp]),
     "qipx_channel_passes": (_int, [_u32, C.POINTER(QipxChannel), _u64, _u64p, _u64p]),

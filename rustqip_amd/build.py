@@ -12,10 +12,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 # one translation unit per concern (csrc/qip_internal.h lists them); compiled in parallel, linked into ONE library whose
 # only exports are the C ABI (csrc/exports.map)
-UNITS = ["qip_core", "qip_launch", "qip_tile_sched", "qip_circuit", "qip_tile_interp", "qip_jit", "qip_slice", "qip_host", "qip_measure", "qip_pauli", "qip_function", "qip_multiplex", "qip_channel", "qip_dist"]
+UNITS = ["qip_core", "qip_launch", "qip_tile_sched", "qip_circuit", "qip_tile_interp", "qip_jit", "qip_slice", "qip_host", "qip_measure", "qip_pauli", "qip_function", "qip_multiplex", "qip_qft", "qip_channel", "qip_dist"]
 HEADERS = [os.path.join(CSRC, h) for h in ("qip_kernels.h", "qip_internal.h", "qip_jit.h", "qip_tile.h", "qip_tile_wire.h", "qip_pauli_plan.h",
                                                "qip_pauli_kernels.h", "qip_diag_plan.h", "qip_diag_kernels.h", "qip_function_plan.h", "qip_function_kernels.h",
-                                               "qip_multiplex_plan.h", "qip_multiplex_kernels.h", "qip_channel_plan.h", "qip_channel_kernels.h")] + [
+                                               "qip_multiplex_plan.h", "qip_multiplex_kernels.h", "qip_qft_plan.h", "qip_qft_kernels.h",
+                                               "qip_channel_plan.h", "qip_channel_kernels.h")] + [
     os.path.join(HERE, "..", "include", "qip_hip.h"), os.path.join(HERE, "..", "include", "qip_hip_debug.h"),
     os.path.join(HERE, "..", "include", "qip_hipx.h")]
 OBJDIR = os.path.join(HERE, "build")

@@ -15,6 +15,8 @@
 //                     C++) and qip_function_kernels.h; its table travels through qip_pauli.hip's table buffer
 //   qip_multiplex.hip multiplexed 1- and 2-qubit gates by table (qipx_state_apply_multiplexed), over qip_multiplex_plan.h (plain
 //                     C++) and qip_multiplex_kernels.h; its table travels through the same buffer
+//   qip_qft.hip       the quantum Fourier transform of a register in FFT passes (qipx_state_apply_qft), over qip_qft_plan.h (plain
+//                     C++) and qip_qft_kernels.h; its twiddle tables travel through the same buffer
 //   qip_channel.hip   noise channels by trajectories (qipx_state_apply_reduce, qipx_state_apply_channels), over qip_channel_plan.h
 //                     (plain C++) and qip_channel_kernels.h
 //   qip_dist.hip      the sharded state (planner, pack sweep, exchange)

@@ -280,6 +280,21 @@ def multiplexed_table_bytes(n: int, select, targets, dtype=np.complex128) -> int
     return int(out.value)
 
 
+def _qft_args(qubits, inverse, reversed):
+    reg = np.ascontiguousarray(np.asarray(list(qubits), dtype=np.uint64).reshape(-1))
+    flags = (1 if inverse else 0) | (2 if reversed else 0)
+    return (reg.ctypes.data_as(C.POINTER(C.c_uint64)), len(reg), flags), reg
+
+
+def qft_passes(n: int, qubits, inverse: bool = False, reversed: bool = False, dtype=np.complex128) -> int:
+    """passes over the vector HipState.apply_qft makes for this register on an n-qubit state of `dtype` (include/qip_hipx.h:
+    qipx_qft_passes; host-only, the call's own checks of the register)"""
+    args, _keep = _qft_args(qubits, inverse, reversed)
+    out = C.c_uint32(0)
+    _check(_ffi.lib.qipx_qft_passes(_dtype_of(np.empty(0, dtype=dtype)), int(n), *args, C.byref(out)))
+    return int(out.value)
+
+
 def _channel_args(channels):
     """(qipx_channel array, count, what keeps its pointers alive, operators per channel) from (qubits, kraus) pairs or objects with
     those attributes; kraus: `count` matrices of 2^k x 2^k, bit i of a row = qubit qubits[i]"""
@@ -706,6 +721,30 @@ class HipState:
         (6.0 - 6.3 against 5.3 - 6.1 ms) and on 3 - 4 qubits in Complex<f32> (2.9 - 3.1 against 2.7 - 2.9 ms)."""
         args, _keep = _multiplexed_args(select, targets, matrices)
         _check(_ffi.lib.qipx_state_apply_multiplexed(self._h, *args))
+
+    def apply_qft(self, qubits, inverse: bool = False, reversed: bool = False) -> None:
+        """The quantum Fourier transform of the register `qubits` (bit i of its value = qubit qubits[i], anywhere, any order), in
+        place, for every setting of the other qubits (include/qip_hipx.h: qipx_state_apply_qft):
+        new[y] = 2^(-m/2) sum_x exp(+-2 pi i x y / 2^m) old[x], the minus sign with `inverse`.  `reversed` leaves the forward
+        result with the register's bits in reversed order, and reads the inverse's input in that order: the pair is the identity
+        and neither pays for a bit reversal.  FFT passes over LDS tiles: one pass per six register qubits outside the six low
+        index bits, plus one bit-reversal sweep (through the scratch buffer) for natural order when that is more than one pass.
+        Per fibre within 8 m u of the exact transform in the 2-norm.  Queued on the handle's stream: returns without waiting.
+        Measured at n = 30 (profiles/qft.md), Complex<f64> / Complex<f32>, beside one H gate pass of 5.3 / 2.8 ms: 12 qubits inside
+        the low index bits 10.4 - 10.6 / 7.9 ms (one pass), 12 qubits on the top bits 14.4 / 9.9 ms reversed and 19.7 / 12.5 ms natural,
+        16 on the top bits 21.4 / 14.3 and 26.7 / 16.8 ms, the whole register 34.5 / 24.7 ms reversed and 40.9 / 28.4 ms natural.
+        fourier.qft_ops through default apply_ops costs 1.22 - 2.35 / 1.04 - 1.89 times the call.  As compiled IEEE-equal sweeps
+        (tile = 1 + tile_jit) it is slower than the call on every shape in Complex<f64>, but in Complex<f32> the call LOSES on 12 low
+        qubits reversed (7.86 against 7.20 ms) and on 16 qubits (16.84 against 16.76, 14.31 against 13.56 ms).  To the 1e-12 mode (tile
+        = 2 + tile_jit + tile_fma + tile_merge) the call LOSES on the whole register (40.9 against 35.1 and 34.5 against 28.4 ms;
+        28.4 against 20.2 and 24.7 against 16.9 ms) and, in Complex<f32>, on 12 low qubits reversed (7.86 against 6.15 ms) and on
+        16 qubits (16.8 against 16.2, 14.3 against 13.2 ms); it wins on the other shapes by 1.05 - 1.52 / 1.03 - 1.12 times."""
+        args, _keep = _qft_args(qubits, inverse, reversed)
+        _check(_ffi.lib.qipx_state_apply_qft(self._h, *args))
+
+    def qft_passes(self, qubits, inverse: bool = False, reversed: bool = False) -> int:
+        """how many passes over the vector apply_qft makes for this register (host-only)"""
+        return qft_passes(self.n, qubits, inverse, reversed, dtype=self.np_dtype)
 
     def _partner(self, other: "HipState", what: str) -> None:
         if not isinstance(other, HipState):

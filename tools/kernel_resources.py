@@ -19,7 +19,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNEL_UNITS = ("qip_launch", "qip_circuit", "qip_tile_interp", "qip_slice", "qip_host", "qip_measure", "qip_pauli", "qip_function", "qip_multiplex", "qip_channel", "qip_dist")  # the units that launch kernels
+KERNEL_UNITS = ("qip_launch", "qip_circuit", "qip_tile_interp", "qip_slice", "qip_host", "qip_measure", "qip_pauli", "qip_function", "qip_multiplex", "qip_qft", "qip_channel", "qip_dist")  # the units that launch kernels
 
 
 def build_flags():
